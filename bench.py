@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: image-text pairs/s of the Mammo-CLIP contrastive pre-training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the outputs of the last timed step when --dump-outputs
+is given, and prints the JSON line: the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, steps,
+warmup, ...) and `config`.  Everything else it can measure or check -- the roofline objects, whole_step, n8_load,
+cpu_baseline, parity / parity_build, the collective evidence of N > 1 runs -- runs only with --full.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned and changed, as float32 .npy
+files: loss_<term>.npy (every term of the step's loss dict) and params_sample.npy (a fixed, seeded sample of at most 4096
+elements of every parameter tensor after the optimizer update, in named_parameters order).  Weights and inputs are seeded,
+so the same arguments give the same inputs run to run; the backward's reduction order is not fixed, so two runs agree to
+rounding (cfg4: loss ~2e-5 relative, parameters ~1e-6), not bit for bit.
 
 N > 1: one process per GPU over RCCL.  Either the driver launches the ranks (``python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N``: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment), or a
@@ -18,7 +29,7 @@ micro-batching costs k - keep extra forwards per step of k micro-batches (engine
 the last `keep` micro-batches are forwarded once, graph kept; 2 full graphs = 232 GB, or all 4 graphs of the N = 8 load
 with the MBConv recompute mode 3).  At N = 1 a step is 32 micro-batches (about 8.5 s in round 5).  "--workload cfg3" is BASELINE configs[2], 32 pairs per GPU in one pass (weak scaling).
 
-The JSON line carries, besides the contract fields:
+With --full the JSON line carries, besides the contract fields:
   roofline     -- the dominant kernel class of THIS run.  The last warm-up step is run with HIP events around every C-ABI
                   launch (all ~70 entry points, keyed by entry point + shape class, e.g. "mc_dwconv_fwd:k5s1"); the three
                   classes with the most GPU time are then bracketed by HIP events on the launch stream at every launch
@@ -153,14 +164,37 @@ def synth_batch_gpu(b, H, W, T, device, seed, views=2):
     return batch
 
 
+DUMP_SAMPLE = 4096             # elements per parameter tensor in the --dump-outputs sample
+
+
+def dump_outputs(out_dir, model, ld):
+    """--dump-outputs: the last timed step's loss terms and a fixed, seeded sample of every parameter tensor after its
+    optimizer update, as float32 .npy files (about 5.5 MB for EfficientNet-B5 + BERT-base).  (Gradients are not dumped:
+    the next step discards them, and their summation order varies run to run.)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in ld.items():
+        np.save(os.path.join(out_dir, f"loss_{k}.npy"), v.detach().float().reshape(-1).cpu().numpy())
+    g = torch.Generator().manual_seed(0)
+    params = []
+    for _, p in model.named_parameters():
+        n = p.numel()
+        idx = (torch.randint(n, (DUMP_SAMPLE,), generator=g) if n > DUMP_SAMPLE else torch.arange(n)).to(p.device)
+        params.append(p.detach().reshape(-1)[idx].float())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(params).cpu().numpy())
+
+
 def cpu_baseline(arch_name, H, W, T, budget_s=80.0):
     """CPU oracle (port of the reference path) on the host cores of this box: ONE full training step (train-mode forward
     + loss + backward + AdamW) of a bounded sample -- 1 pair = 2 images + 2 reports at the workload's size.  Protocol
     (bounded): one untimed warm-up step, then the median of up to 3 timed steps within ``budget_s``
     (at least one timed step)."""
     from oracle import arch as oarch, bert as obert, clip as oclip, loss as oloss, weights as ow
-    cores = os.cpu_count() or 1
-    threads = min(cores, 64)     # measured on the MI355X host: 64 threads 46 s vs 128 threads 79 s for the same sample
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    # measured on the MI355X host: 64 threads 46 s vs 128 threads 79 s for the same sample; an OMP_NUM_THREADS allowance
+    # below that is honoured (more threads than the CPUs granted only oversubscribe them)
+    omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+    threads = min(cores, int(omp) if omp.isdigit() and int(omp) > 0 else cores, 64)
     torch.set_num_threads(threads)
     arch = oarch.build_arch(arch_name)
     cfg = obert.BertShape()
@@ -197,6 +231,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: roofline / whole_step (survey step and "
+                         "HIP events around launches), one-stream steps, n8_load, parity / parity_build, cpu_baseline, collective evidence")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss terms and a seeded sample of the updated parameters to DIR/*.npy")
     ap.add_argument("--workload", default="cfg4", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="pairs per GPU (0 = workload default)")
     ap.add_argument("--micro-batches", type=int, default=1,
@@ -228,6 +267,8 @@ def main():
                     help="16-bit storage / MFMA operand build of the kernel library (default: MC_STORAGE or bf16 -- BASELINE's dtype; "
                          "f16 = the reference's AMP dtype with a dynamic loss scale, the parity configuration of DESIGN.md (c))")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.storage:
         os.environ["MC_STORAGE"] = args.storage        # read when the package is imported (below; the spawned ranks inherit it)
 
@@ -258,7 +299,7 @@ def main():
     # evidence that the collectives ran on RCCL with N ranks: RCCL's own INIT log goes to a per-process file
     # (NCCL_DEBUG_FILE), rank 0 reads its communicator line ("... nranks N ...") back after the first collective
     rccl_log = None
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and os.environ.get("MC_DIST_BACKEND", "nccl") == "nccl":
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) > 1 and os.environ.get("MC_DIST_BACKEND", "nccl") == "nccl":
         import tempfile
         rccl_log = os.path.join(tempfile.gettempdir(), f"mc_rccl_{os.getpid()}.log")
         os.environ.setdefault("NCCL_DEBUG", "INFO")
@@ -321,7 +362,7 @@ def main():
             torch.cuda.synchronize()
 
     dist_info = None
-    if world > 1:
+    if args.full and world > 1:
         ones = torch.ones(1, device=device)
         dist.all_reduce(ones)                      # SUM of one per rank over the job's backend: = the ranks that took part
         dist_info = {"backend": dist.get_backend(), "allreduce_of_ones": int(ones.item()), "rccl_ranks": None}
@@ -336,21 +377,24 @@ def main():
                 if m:
                     dist_info["rccl_ranks"] = max(int(v) for v in m)
 
-    # warm-up; the LAST warm-up step (an extra step when --warmup 0) is the survey step: HIP events around every C-ABI
-    # launch -> GPU time per kernel class -> the three classes the timed steps bracket
-    for _ in range(max(args.warmup - 1, 0)):
+    # warm-up; with --full the LAST warm-up step (an extra step when --warmup 0) is the survey step: HIP events around every
+    # C-ABI launch -> GPU time per kernel class -> the three classes the timed steps bracket
+    for _ in range(max(args.warmup - 1, 0) if args.full else args.warmup):
         ld = trainer.step(batch, args.micro_batches)
     sync()
-    survey = L.OpTimer()
-    L.TIMER = survey
-    ld = trainer.step(batch, args.micro_batches)
-    sync()
-    L.TIMER = None
-    raw = survey.summary()
-    ssum = merged(raw)
-    del survey
-    top = [k for k, v in sorted(ssum.items(), key=lambda kv: -kv[1][1]) if v[2] > 0 or v[3] > 0][:3]
-    timer = L.OpTimer(keys=None if args.op_profile else [k for k in raw if class_key(k) in top])
+    raw, ssum, top, timer = {}, {}, [], None
+    if args.full:
+        survey = L.OpTimer()
+        L.TIMER = survey
+        ld = trainer.step(batch, args.micro_batches)
+        sync()
+        L.TIMER = None
+        raw = survey.summary()
+        ssum = merged(raw)
+        del survey
+        top = [k for k, v in sorted(ssum.items(), key=lambda kv: -kv[1][1]) if v[2] > 0 or v[3] > 0][:3]
+    if args.full or args.op_profile:
+        timer = L.OpTimer(keys=None if args.op_profile else [k for k in raw if class_key(k) in top])
     L.TIMER = timer
     torch.cuda.reset_peak_memory_stats()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]     # per-step spread (no sync inside the region)
@@ -368,10 +412,12 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
     loss_val = float(ld["total"])
-    raw_timed = timer.summary()
+    raw_timed = timer.summary() if timer is not None else {}
     summ = merged(raw_timed)
     peak_gb = torch.cuda.max_memory_allocated() / 1e9
     peak_res_gb = torch.cuda.max_memory_reserved() / 1e9
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, ld)
 
     # Kernel rooflines need launch durations that belong to ONE kernel.  With the encoder chains on separate streams a
     # bracketed launch shares the GPU with launches of the other chains: the HIP-event time around it is no longer that
@@ -380,7 +426,7 @@ def main():
     # step first: the allocator pools of the side streams are released and the main pool regrows); the shared durations of the
     # timed region are reported beside them (`in_timed_region`).
     summ_x, xsteps = None, 0
-    if streams and not args.roofline_in_timed_region:
+    if args.full and streams and not args.roofline_in_timed_region:
         clipmod._STREAMS = 0
         trainer.optimizer.zero_grad(set_to_none=True)
         torch.cuda.empty_cache()
@@ -397,7 +443,7 @@ def main():
         clipmod._STREAMS = streams
 
     n8 = None
-    if world == 1 and args.workload == "cfg4" and strong and not args.no_n8_load and not single:
+    if args.full and world == 1 and args.workload == "cfg4" and strong and not args.no_n8_load and not single:
         # the step one GPU runs at N = 8 (128 pairs = 4 micro-batches, recompute mode 3, four kept graphs), no communication
         del batch, ld
         trainer.optimizer.zero_grad(set_to_none=True)
@@ -421,7 +467,7 @@ def main():
 
     stat_tapes_on = bool(getattr(trainer, "stat_tapes", False)) and args.micro_batches > args.keep_graphs
     parity = parity_build = None
-    if rank == 0 and world == 1 and not args.no_parity and args.workload in ("cfg2", "cfg3", "cfg4") and not single:
+    if args.full and rank == 0 and world == 1 and not args.no_parity and args.workload in ("cfg2", "cfg3", "cfg4") and not single:
         # checker legs, after every timed region: free the benchmark's memory first
         try:
             del batch, ld
@@ -448,7 +494,7 @@ def main():
             del model
             torch.cuda.empty_cache()
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), "--storage", "f16", "--parity-child", "--workload", args.workload,
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--storage", "f16", "--parity-child", "--workload", args.workload,
                    "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-n8-load", "--roofline-in-timed-region"]
             if args.batch:
                 cmd += ["--batch", str(args.batch)]
@@ -470,7 +516,7 @@ def main():
                  [os.path.join(ROOT, "profiles", f"r{r:02d}_roofline_traffic.json") for r in (6, 5, 4, 3)])
         tpath = next((q for q in cands if os.path.exists(q)), "")
         own_mix = tpath.endswith(f"_{args.workload}.json") or args.workload == "cfg3"
-        tj = json.load(open(tpath)) if tpath and args.workload in ("cfg3", "cfg4") and not args.batch else {}
+        tj = json.load(open(tpath)) if args.full and tpath and args.workload in ("cfg3", "cfg4") and not args.batch else {}
         # the PMC bytes were collected on the cfg3 launch mix (32 pairs in one pass): the same 32-pair launches as cfg4's
         # micro-batches, but cfg4 adds the re-forward launches -- its per-class launch MIX differs, so the ratio of `traffic`
         # to `algorithmic_bytes_per_launch` is only meaningful for --workload cfg3
@@ -530,19 +576,20 @@ def main():
                        "streams": streams,
                        "step_ms": {"first": round(step_ms[0], 1), "last": round(step_ms[-1], 1), "min": round(min(step_ms), 1),
                                    "max": round(max(step_ms), 1)}},     # rank 0's steps (HIP events on the main stream, which joins the chains)
-            "roofline": first, "roofline_runner_up": second, "roofline_third": third,
         }
-        # the whole step against both roofs: algorithmic bytes / flops of every launch of ONE step (the survey step's tags,
-        # ops._note: each kernel reads its inputs and writes its outputs once) over the measured step time -- independent of
-        # how the launches overlap
-        sb, sf = sum(v[2] for v in ssum.values()), sum(v[3] for v in ssum.values())
-        res["whole_step"] = {"algorithmic_gb_per_step": round(sb / 1e9, 1), "algorithmic_tflop_per_step": round(sf / 1e12, 2),
-                             "hbm_gb_per_s": round(sb / 1e9 / (ms * 1e-3), 1), "hbm_frac": round(sb / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4),
-                             "mfma_tflop_per_s": round(sf / 1e12 / (ms * 1e-3), 1), "mfma_frac": round(sf / (ms * 1e-3) / (MFMA_PEAK_TFS * 1e12), 4),
-                             # 497 GB per 32-pair B5 step when every conv reads its input and writes its output once
-                             "survey_8d_min_gb_per_step": (round(497.0 * b / 32, 1) if args.workload in ("cfg3", "cfg4", "cfg5") else None),
-                             "hbm_frac_of_survey_min": (round(497e9 * b / 32 / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4) if args.workload in ("cfg3", "cfg4", "cfg5") else None),
-                             "note": "per GPU; bytes / flops as tagged per launch (sum over the kernels' own inputs + outputs, i.e. the traffic of THIS pass structure, not SURVEY 8d's one-read-one-write minimum)"}
+        if args.full:
+            res.update(roofline=first, roofline_runner_up=second, roofline_third=third)
+            # the whole step against both roofs: algorithmic bytes / flops of every launch of ONE step (the survey step's tags,
+            # ops._note: each kernel reads its inputs and writes its outputs once) over the measured step time -- independent of
+            # how the launches overlap
+            sb, sf = sum(v[2] for v in ssum.values()), sum(v[3] for v in ssum.values())
+            res["whole_step"] = {"algorithmic_gb_per_step": round(sb / 1e9, 1), "algorithmic_tflop_per_step": round(sf / 1e12, 2),
+                                 "hbm_gb_per_s": round(sb / 1e9 / (ms * 1e-3), 1), "hbm_frac": round(sb / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4),
+                                 "mfma_tflop_per_s": round(sf / 1e12 / (ms * 1e-3), 1), "mfma_frac": round(sf / (ms * 1e-3) / (MFMA_PEAK_TFS * 1e12), 4),
+                                 # 497 GB per 32-pair B5 step when every conv reads its input and writes its output once
+                                 "survey_8d_min_gb_per_step": (round(497.0 * b / 32, 1) if args.workload in ("cfg3", "cfg4", "cfg5") else None),
+                                 "hbm_frac_of_survey_min": (round(497e9 * b / 32 / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4) if args.workload in ("cfg3", "cfg4", "cfg5") else None),
+                                 "note": "per GPU; bytes / flops as tagged per launch (sum over the kernels' own inputs + outputs, i.e. the traffic of THIS pass structure, not SURVEY 8d's one-read-one-write minimum)"}
         if n8 is not None:
             res["n8_load"] = n8
         if parity is not None:
@@ -552,7 +599,7 @@ def main():
         if dist_info is not None:
             res["rccl_ranks"] = dist_info["rccl_ranks"]
             res["dist"] = dist_info
-        if world == 1 and not args.no_cpu_baseline and not single:
+        if args.full and world == 1 and not args.no_cpu_baseline and not single:
             try:
                 res["cpu_baseline"] = cpu_baseline(arch_name, H, W, T)
             except Exception as e:                # pragma: no cover

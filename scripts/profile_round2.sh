@@ -6,8 +6,8 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 OUT=$R/gpurun_out/prof_r2; mkdir -p $OUT
-C4="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline"
-C3="python $R/bench.py --workload cfg3 --steps 1 --warmup 1 --no-cpu-baseline"
+C4="python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline"
+C3="python $R/bench.py --full --workload cfg3 --steps 1 --warmup 1 --no-cpu-baseline"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4 -- $C4 > $OUT/c4.log 2>&1
 cp $(ls /tmp/p_c4/*/*kernel_stats.csv | head -1) $OUT/cfg4_kernel_stats.csv
 cp $(ls /tmp/p_c4/*/*agent_info.csv | head -1) $OUT/agent_info.csv

@@ -4,8 +4,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 OUT=$R/gpurun_out/prof_r3; mkdir -p $OUT
 MODE=${1:-stats}
-C4="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline"
-C3="python $R/bench.py --workload cfg3 --steps 1 --warmup 1 --no-cpu-baseline"
+C4="python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline"
+C3="python $R/bench.py --full --workload cfg3 --steps 1 --warmup 1 --no-cpu-baseline"
 if [ "$MODE" = "stats" ] || [ "$MODE" = "all" ]; then
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c3 -- $C3 > $OUT/c3.log 2>&1
   cp $(ls /tmp/p_c3/*/*kernel_stats.csv | head -1) $OUT/cfg3_kernel_stats.csv

@@ -4,8 +4,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 OUT=$R/gpurun_out/prof_r5; mkdir -p $OUT
 MODE=${1:-stats}
-C4="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline"
-C3="python $R/bench.py --workload cfg3 --steps 1 --warmup 1 --no-cpu-baseline"
+C4="python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline"
+C3="python $R/bench.py --full --workload cfg3 --steps 1 --warmup 1 --no-cpu-baseline"
 if [ "$MODE" = "stats" ] || [ "$MODE" = "all" ]; then
   # the default run (encoder chains on three streams: kernel durations are SHARED with concurrent launches) ...
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c3 -- $C3 --roofline-in-timed-region > $OUT/c3.log 2>&1
@@ -53,7 +53,7 @@ if [ "$MODE" = "pmc4s" ]; then
   # HBM traffic on the DEFAULT run's launch mix, sampled: 128 pairs as 4 micro-batches with ONE kept graph = 4
   # graph-less forwards' worth of launches, 3 re-forwards with replayed statistics, 4 backwards -- the per-micro-batch launch mix
   # of the N = 1 run (25 of 32 micro-batches re-forwarded) at 1 / 8 of its launches, so a counter pass takes minutes
-  C4S="python $R/bench.py --batch 128 --micro-batches 4 --keep-graphs 1 --steps 1 --warmup 1 --no-cpu-baseline --no-n8-load"
+  C4S="python $R/bench.py --full --batch 128 --micro-batches 4 --keep-graphs 1 --steps 1 --warmup 1 --no-cpu-baseline --no-n8-load"
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c4s -- $C4S > $OUT/c4s.log 2>&1
   cp $(ls /tmp/p_c4s/*/*kernel_stats.csv | head -1) $OUT/cfg4_kernel_stats.csv
   i=0

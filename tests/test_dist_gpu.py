@@ -423,7 +423,7 @@ def test_bench_launches_two_ranks_and_prints_one_json_line():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg1", "--steps", "1",
-                        "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
     js = json.loads(lines[0])
@@ -432,3 +432,29 @@ def test_bench_launches_two_ranks_and_prints_one_json_line():
     # the line says which backend the job's collectives ran on and how many ranks took part in one (round 5; over RCCL
     # "rccl_ranks" additionally carries the rank count RCCL's own INIT log reports -- gloo has no such log: None here)
     assert js["dist"]["backend"] == "gloo" and js["dist"]["allreduce_of_ones"] == 2 and js["rccl_ranks"] is None, js["dist"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain ``python bench.py --gpus 1`` run does only the headline: the contract fields, no --full objects (roofline,
+    whole_step, parity, cpu_baseline); --dump-outputs writes the last timed step's loss terms and the parameter sample as
+    float32 .npy files within 64 MB, and the dumped total loss is the one the line reports."""
+    import json
+
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfg1", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    js = json.loads(lines[0])
+    assert js["steps"] == 3 and js["warmup"] == 1 and js["value"] > 0 and js["ms_per_step"] > 0 and js["higher_is_better"] is True
+    assert abs(js["value"] - js["config"]["global_batch"] / (js["ms_per_step"] * 1e-3)) <= 1e-2 * js["value"]
+    for k in ("roofline", "whole_step", "parity", "parity_build", "cpu_baseline", "n8_load", "dist"):
+        assert k not in js, k
+    files = sorted(p.name for p in out.iterdir())
+    assert {"loss_total.npy", "params_sample.npy"} <= set(files), files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    arrs = {f: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+    assert abs(float(arrs["loss_total.npy"][0]) - js["config"]["loss"]) <= 1e-4

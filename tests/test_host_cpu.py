@@ -86,12 +86,12 @@ def test_abi_argument_validation_without_gpu():
     assert b"stem_im2col_u8" in lib.mc_last_error()
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     """ctypes mirrors must have the C struct sizes (checked against a C compile of the header)"""
     src = '#include <stdio.h>\n#include "mammoclip_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(mc_gemm_args),' \
           ' sizeof(mc_dwconv_args), sizeof(mc_bnact_args), sizeof(mc_gemm_rows_args), sizeof(mc_wgrad_rows_args),' \
           ' sizeof(mc_adamw_tensor));return 0;}\n'
-    exe = os.path.join("/tmp", "mc_sizes_test")
+    exe = str(tmp_path / "mc_sizes_test")
     with open(exe + ".c", "w") as f:
         f.write(src)
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), exe + ".c", "-o", exe], check=True)
