@@ -196,9 +196,10 @@ def _bn_stats(partials, count, bn: nn.BatchNorm2d, training: bool):
     return ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS)
 
 
-def _conv_stats(fn, training, *a, **kw):
-    """run a producer that can leave BatchNorm statistics partials (stats=True -> (y, partials)); a replaying tape needs none"""
-    if training and _replaying():
+def _conv_stats(fn, training, *a, stats=True, **kw):
+    """run a producer that can leave BatchNorm statistics partials (stats=True -> (y, partials)); a replaying tape needs none,
+    nor does a backward that rebuilds y (stats=False)"""
+    if not stats or (training and _replaying()):
         return fn(*a, **kw), None
     return fn(*a, stats=True, **kw)
 
@@ -230,7 +231,7 @@ class _StemFn(torch.autograd.Function):
         its epilogue and leaves the BatchNorm reductions in the link."""
         n, _, h, wd = x.shape
         l, r, t, b = mod.stem_pad
-        oh, ow = _out_extent(h, t, b, 3, 2), _out_extent(wd, l, r, 3, 2)
+        _, oh, ow = mod.stem_geo(n, h, wd)
         c0 = w.shape[0]
         patches = ops.stem_im2col(x, l, t, oh, ow)
         wb = ops.stem_weight_prep(w)
@@ -241,7 +242,6 @@ class _StemFn(torch.autograd.Function):
         ctx.raw = (x.mean, x.std) if isinstance(x, ops.RawImages) else None
         ctx.save_for_backward(x.data if ctx.raw else x, e)
         ctx.link = link
-        mod._geo = (n, oh, ow)
         if link is not None:
             link.st, link.part = st, None
             return e.detach()               # (a new tensor object: autograd must not return a saved input as the output)
@@ -278,81 +278,74 @@ class _StemLink:
         self.st, self.part = None, None
 
 
-def _expand_conv(blk, x, we, rows, training=False, recompute=False):
-    """_expand_conv of one block: e [rows, cexp] bf16 + the BatchNorm0 column-statistic partials (deterministic: the
-    backward's recompute mode reproduces the forward's tensor bit for bit)."""
-    a = blk.args
-    if blk.fp8 and a.cin % 16 == 0 and not ops._rows_ok(rows, a.cexp, a.cin, None, 0):
+def _expand_conv(pl, x, we, stats=True):
+    """_expand_conv of one block: (e [rows, cexp] bf16, BatchNorm0 column-statistic partials) (deterministic: the backward's
+    rebuild, stats=False, reproduces the forward's tensor bit for bit)."""
+    if pl.fp8_expand:
         # config #5: fp8 (e4m3, per-tensor scale) activations and weights on the fp8 MFMA; BatchNorm statistics
         # and everything downstream stay on the bf16 / fp32 path; backward uses the bf16 tensors (straight-through)
-        r = ops.linear_fwd_fp8(x, we, stats=True)
-        return r[0] if recompute else r
-    if recompute:
-        return ops.linear_fwd(x, we)
-    return _conv_stats(ops.linear_fwd, training, x, we)
+        return ops.linear_fwd_fp8(x, we, stats=True)
+    return _conv_stats(ops.linear_fwd, pl.training, x, we, stats=stats)
+
+
+def _depthwise(blk, pl, x, e, we, wkkc, pro0, stats=True):
+    """depthwise stage of one block: (d [n*oh*ow, cexp] bf16, BatchNorm1 partials) from the block input x (fused expand +
+    depthwise launch: from the UNROUNDED expand output) or from e / the linked stem output x (pro0 = the BatchNorm0 + swish
+    prologue).  The backward rebuilds d through this very function (stats=False): same launch, bit for bit."""
+    if pl.xdw:
+        return _conv_stats(ops.mbconv_xdw_fwd, pl.training, x, we, pro0, wkkc, *pl.dw, stats=stats)
+    return _conv_stats(ops.dwconv_fwd, pl.training, e if blk.args.expand != 1 else x, wkkc, *pl.dw, stats=stats, pro=pro0)
+
+
+def _project_conv(pl, d, act1, st1, gate, wp, stats=True):
+    """_project_conv of one block: (p [n*oh*ow, cout] bf16, BatchNorm2 partials)"""
+    ohw = pl.oh * pl.ow
+    if pl.fp8_project:
+        wg = ops.gate_weights(wp, gate)                           # [n, cout, cexp] bf16: the SE gate folded into the weights
+        return ops.linear_fwd_fp8(act1, wg, stats=True, batch_w=(pl.n, ohw))
+    # stored activation: only the SE gate is applied; else BN1 + SiLU + gate while the GEMM stages its A operand
+    src, pro = (act1, (None, None, gate, ohw)) if pl.keep_act else (d, (st1.scale, st1.shift, gate, ohw))
+    return _conv_stats(ops.linear_fwd, pl.training, src, wp, stats=stats, pro=pro)
 
 
 class _MBConvFn(torch.autograd.Function):
-    """One MBConvBlock, forward + hand-derived backward [ref: efficientnet_custom.py:91-132]."""
+    """One MBConvBlock, forward + hand-derived backward [ref: efficientnet_custom.py:91-132].  Every path choice of the pair is
+    made once, by ``MBConvBlock.plan``, when the forward runs; the backward reads the plan stored with the graph."""
 
     @staticmethod
-    def forward(ctx, x, rowscale, blk, n, h, w, *params):
+    def forward(ctx, x, rowscale, blk, n, h, w, recording, link, *params):
         a = blk.args
-        training = blk.training
-        k, s = a.k, a.s
-        l, r, t, b = a.pad
-        oh, ow = _out_extent(h, t, b, k, s), _out_extent(w, l, r, k, s)
-        hw, ohw = h * w, oh * ow
-        saved = {}
-        rc = blk.recompute
-        wkkc = ops.transpose_f32(blk._depthwise_conv.weight.view(a.cexp, k * k), cache=True)
-        xdw = efree = False
+        pl = blk.plan(n, h, w, recording)
+        training, ohw = pl.training, pl.oh * pl.ow
+        wkkc = blk.w_taps()
+        e = we = st0 = gram = None
         if a.expand != 1:
-            we = ops.cast_bf16(blk._expand_conv.weight.view(a.cexp, a.cin))
-            # round 6: where no backward needs the expanded tensor e stored (no graph, or a recompute mode that rebuilds it), the
-            # expand conv runs inside the depthwise launch's staging and e never exists in HBM: BatchNorm0's batch statistics
-            # then come from the Gram matrix of the block input (one pass over x, 6 x narrower than e), from the statistics
-            # tape of a re-forward, or from the running statistics (eval)
-            # (autograd runs Function.forward with grad mode off and reports needs_input_grad from requires_grad alone:
-            # whether a graph is being recorded is noted by MBConvBlock.forward before the call)
-            xdw = (rc >= 1 or not blk.__dict__.get("_recording", True)) and blk.xdw_ok(n, h, w, oh, ow)
-            # ... and stride-1 3x3 blocks whose backward forms its e rows from x as well (ops.dwconv_bwd_fused with xw) and
-            # folds the BatchNorm0 backward into the expand conv's gradient GEMMs never need e anywhere: fused forward always
-            efree = blk.efree_ok(n, h, w, oh, ow)
-            xdw = xdw or efree
-            gram = None
-            if xdw:
+            we = blk.w_expand()
+            if pl.xdw:
+                # e never exists in HBM: BatchNorm0's batch statistics come from the Gram matrix of the block input (one pass
+                # over x, 6 x narrower than e), from the statistics tape of a re-forward, or from the running statistics (eval).
                 # x^T x and colsum(x) of the Gram statistics pass are what the folded BatchNorm0 backward of this block needs
                 # again: they stay in the graph (a few KB) and travel on the statistics tape to the re-forward's backward
                 if training and _replaying():
                     part0, gram = None, _TAPE.get()
                 elif training:
-                    part0, gram = ops.bn_gram_partials(x, we, n * hw)
+                    part0, gram = ops.bn_gram_partials(x, we, n * h * w)
                     if _TAPE is not None:
                         _TAPE.put(gram)
                 else:
                     part0 = None
-                st0 = _bn_stats(part0, n * hw, blk._bn0, training)
-                e = None
-                d, part1 = _conv_stats(ops.mbconv_xdw_fwd, training, x, we, (st0.scale, st0.shift), wkkc, n, h, w, a.cexp, k, s,
-                                       l, t, oh, ow)
             else:
-                e, part0 = _expand_conv(blk, x, we, n * hw, training)
-                st0 = _bn_stats(part0, n * hw, blk._bn0, training)
-            dw_in, pro0 = e, (st0.scale, st0.shift)
-            saved.update(we=we, e=None if (rc >= 1 or efree) else e, st0=st0, gram=gram)
+                e, part0 = _expand_conv(pl, x, we)
+            st0 = _bn_stats(part0, n * h * w, blk._bn0, training)
+            pro0 = (st0.scale, st0.shift)
         else:
             # block 0 behind a linked stem: x is the stem's RAW conv output, its bn0 + swish is this block's prologue
-            link = blk.__dict__.pop("_in_link", None)
-            dw_in, pro0 = x, ((link.st.scale, link.st.shift) if link is not None else None)
-            saved.update(link=link)
-        if not xdw:
-            d, part1 = _conv_stats(ops.dwconv_fwd, training, dw_in, wkkc, n, h, w, a.cexp, k, s, l, t, oh, ow, pro=pro0)
+            pro0 = (link.st.scale, link.st.shift) if link is not None else None
+        d, part1 = _depthwise(blk, pl, x, e, we, wkkc, pro0)
         st1 = _bn_stats(part1, n * ohw, blk._bn1, training)
         # Late stages (project conv on the tiled GEMM): the squeeze pass also stores A = silu(bn1(d)); the project GEMM
         # and its weight gradient then apply only the SE gate instead of re-evaluating BN+SiLU per output tile.
-        keep = not ops._rows_ok(n * ohw, a.cout, a.cexp, None, 0)
-        if keep:
+        if pl.keep_act:
             pooled, act1 = ops.bnact_pool(d, n, ohw, a.cexp, st1.scale, st1.shift, 1, keep_act=True)
         elif training and _replaying():
             pooled, act1 = _TAPE.get(), None                      # (early stages: the squeeze pass only produced this)
@@ -367,71 +360,46 @@ class _MBConvFn(torch.autograd.Function):
                               blk._se_expand.weight.view(a.cexp, a.cse), blk._se_expand.bias)
             if training and _TAPE is not None:
                 _TAPE.put(gate)
-        wp = ops.cast_bf16(blk._project_conv.weight.view(a.cout, a.cexp))
-        if keep and blk.fp8 and a.cexp % 16 == 0 and a.cout > 64:
-            wg = ops.gate_weights(wp, gate)                       # [n, cout, cexp] bf16: the SE gate folded into the weights
-            p, part2 = ops.linear_fwd_fp8(act1, wg, stats=True, batch_w=(n, ohw))
-        elif keep:
-            p, part2 = _conv_stats(ops.linear_fwd, training, act1, wp, pro=(None, None, gate, ohw))
-        else:
-            p, part2 = _conv_stats(ops.linear_fwd, training, d, wp, pro=(st1.scale, st1.shift, gate, ohw))
+        wp = blk.w_project()
+        p, part2 = _project_conv(pl, d, act1, st1, gate, wp)
         st2 = _bn_stats(part2, n * ohw, blk._bn2, training)
         y = ops.bnact_apply(p, n, ohw, a.cout, st2.scale, st2.shift, 0,
                             rowscale=rowscale if a.skip else None, res=x if a.skip else None)
-        # recompute modes (activation memory of a kept graph, see EfficientNet.set_recompute): 1 drops the expanded
-        # tensor e, 2 also the depthwise output d (+ the stored activation of the late stages), 4 also the projection
-        # output p; the backward rebuilds them from the block input x and the saved BatchNorm coefficients
-        saved.update(x=x, d=None if rc >= 2 else d, p=None if rc >= 4 else p, wkkc=wkkc, wp=wp, st1=st1, st2=st2, pooled=pooled, gate=gate,
-                     act1=None if rc >= 2 else act1, keep_act=keep, xdw=xdw, efree=(a.expand != 1 and efree),
-                     rowscale=rowscale if a.skip else None, geo=(n, h, w, oh, ow))
-        ctx.blk, ctx.saved = blk, saved
-        blk._out_geo = (n, oh, ow)
+        # what the plan does not store (recompute modes, see EfficientNet.set_recompute) the backward rebuilds from the block
+        # input x and the saved BatchNorm coefficients; efree is repeated beside the tensors for whoever audits a graph node
+        ctx.blk, ctx.plan, ctx.saved = blk, pl, dict(
+            x=x, e=e if pl.store_e else None, d=d if pl.store_d else None, act1=act1 if pl.store_d else None,
+            p=p if pl.store_p else None, we=we, wkkc=wkkc, wp=wp, pro0=pro0, link=link, st0=st0, st1=st1, st2=st2, gram=gram,
+            pooled=pooled, gate=gate, efree=pl.efree, rowscale=rowscale if a.skip else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        blk, sv = ctx.blk, ctx.saved
+        blk, pl, sv = ctx.blk, ctx.plan, ctx.saved
         a = blk.args
-        n, h, w, oh, ow = sv["geo"]
+        n, h, w, oh, ow = pl.n, pl.h, pl.w, pl.oh, pl.ow
         hw, ohw = h * w, oh * ow
-        k, s = a.k, a.s
-        l, r, t, b = a.pad
+        k, s, l, t = a.k, a.s, a.pad[0], a.pad[2]
         dy = dy.contiguous()
-        x, d, p = sv["x"], sv["d"], sv["p"]
-        st1, st2, gate, pooled = sv["st1"], sv["st2"], sv["gate"], sv["pooled"]
-        e, act1 = sv.get("e"), sv["act1"]
-        efree = bool(sv.get("efree"))
-        if a.expand != 1:
-            st0 = sv["st0"]
-            if e is None and not efree:                      # (recompute modes: same kernels, statistics epilogues off)
-                e = _expand_conv(blk, x, sv["we"], n * hw, recompute=True)
-        link = sv.get("link")
+        x, e, d, p, act1, link, pro0 = sv["x"], sv["e"], sv["d"], sv["p"], sv["act1"], sv["link"], sv["pro0"]
+        st0, st1, st2, gate, pooled = sv["st0"], sv["st1"], sv["st2"], sv["gate"], sv["pooled"]
+        if a.expand != 1 and e is None and not pl.efree:     # (recompute modes: same kernels, statistics epilogues off)
+            e = _expand_conv(pl, x, sv["we"], stats=False)[0]
         if d is None:
-            if sv.get("xdw"):
-                # the forward produced d with the fused launch (from the UNROUNDED expand output): rebuilt the same way, bit for bit
-                d = ops.mbconv_xdw_fwd(x, sv["we"], (st0.scale, st0.shift), sv["wkkc"], n, h, w, a.cexp, k, s, l, t, oh, ow)
-            else:
-                d = ops.dwconv_fwd(e if a.expand != 1 else x, sv["wkkc"], n, h, w, a.cexp, k, s, l, t, oh, ow,
-                                   pro=(st0.scale, st0.shift) if a.expand != 1 else ((link.st.scale, link.st.shift) if link is not None else None))
-            if sv["keep_act"]:
+            d = _depthwise(blk, pl, x, e, sv["we"], sv["wkkc"], pro0, stats=False)[0]
+            if pl.keep_act:
                 act1 = ops.bnact_pool(d, n, ohw, a.cexp, st1.scale, st1.shift, 1, keep_act=True)[1]
         if p is None:                                        # mode 4: the projection conv again, from the rebuilt d
-            if sv["keep_act"] and blk.fp8 and a.cexp % 16 == 0 and a.cout > 64:
-                p = ops.linear_fwd_fp8(act1, ops.gate_weights(sv["wp"], gate), stats=True, batch_w=(n, ohw))[0]
-            elif sv["keep_act"]:
-                p = ops.linear_fwd(act1, sv["wp"], pro=(None, None, gate, ohw))
-            else:
-                p = ops.linear_fwd(d, sv["wp"], pro=(st1.scale, st1.shift, gate, ohw))
+            p = _project_conv(pl, d, act1, st1, gate, sv["wp"], stats=False)[0]
         # y = bn2(p) * rowscale + x
         dp, dg2, db2 = ops.bnact_bwd(p, n, ohw, a.cout, st2, blk._bn2.weight, 0, g=dy, rowscale=sv["rowscale"])
         # project 1x1: p = A1 . wp^T, A1 = silu(bn1(d)) * gate   (A1 is recomputed inside the wgrad GEMM)
-        wp_t = ops.cast_transpose_bf16(blk._project_conv.weight.view(a.cout, a.cexp))      # [cexp, cout]
+        wp_t = blk.w_project(transposed=True)                # [cexp, cout]
         # Early stages (row-streaming shapes, whole 16-row groups per image): dA1 = dp . wp never goes to memory -- the
         # projection's data-gradient GEMM runs TWICE with an elementwise epilogue over d, first for the squeeze-excite /
         # BatchNorm1 sums, then (once the SE backward has produced d loss / d pooled) for the BatchNorm1 + swish backward
         # itself: 1 + 2 passes over the depthwise-site tensor instead of 1 (dgrad) + 2 (sums) + 3 (apply)
-        fuse = FUSE_PROJ_DGRAD and ops.proj_dgrad_fusable(n * ohw, a.cexp, a.cout, ohw)
-        da1 = None if fuse else ops.linear_dgrad(dp, sv["wp"], w_t=wp_t)
+        da1 = None if pl.fuse_proj_dgrad else ops.linear_dgrad(dp, sv["wp"], w_t=wp_t)
         if act1 is not None:
             dwp = ops.linear_wgrad(dp, act1, pro=(None, None, gate, ohw))
             del act1
@@ -439,13 +407,13 @@ class _MBConvFn(torch.autograd.Function):
             dwp = ops.linear_wgrad(dp, d, pro=(st1.scale, st1.shift, gate, ohw))
         # squeeze-excite
         # ONE pass over (d, dA1) yields d loss / d gate AND the ingredients of the bn1-backward reductions
-        sums = ops.proj_dgrad_se_sums(dp, wp_t, d, st1, n, ohw) if fuse else ops.bnact_se_sums(d, da1, n, ohw, a.cexp, st1, 1)
+        sums = ops.proj_dgrad_se_sums(dp, wp_t, d, st1, n, ohw) if pl.fuse_proj_dgrad else ops.bnact_se_sums(d, da1, n, ohw, a.cexp, st1, 1)
         dpooled, dw1, db1, dw2, dbse2 = ops.se_bwd(pooled, gate, sums[0], blk._se_reduce.weight.view(a.cse, a.cexp),
                                                    blk._se_reduce.bias, blk._se_expand.weight.view(a.cexp, a.cse),
                                                    blk._se_expand.bias)
         # bn1 + swish: upstream of swish output = dA1 * gate + dpooled / (oh*ow)
         part1 = ops.bn_partials_from_se_sums(sums, gate, dpooled, 1.0 / ohw)
-        if fuse:
+        if pl.fuse_proj_dgrad:
             coef1, dg1, db1n = ops.bn_bwd_coefs(part1, n * ohw, st1, blk._bn1.weight)
             dd = ops.proj_dgrad_bn_apply(dp, wp_t, d, st1, coef1, gate, dpooled, 1.0 / ohw, ohw)
         else:
@@ -454,18 +422,13 @@ class _MBConvFn(torch.autograd.Function):
         del da1
         # depthwise
         del d
-        if a.expand != 1:
-            dw_in, pro0 = e, (st0.scale, st0.shift)
-        else:
-            dw_in, pro0 = x, ((link.st.scale, link.st.shift) if link is not None else None)
-        wflip = ops.flipped_taps_f32(blk._depthwise_conv.weight.view(a.cexp, k * k)) if s == 1 else None   # 180 degree rotation
+        dw_in = e if a.expand != 1 else x
+        wflip = blk.w_taps(flipped=True) if s == 1 else None   # 180 degree rotation
         # round 5: stride-1 3x3 blocks run the WHOLE depthwise backward as one launch (conv_lane.hip MODE 3): data gradient with
         # the bn0 + swish epilogue AND the weight gradient from one staging of (dd, e) -- 3 passes over the expanded tensor
         # instead of 5; where that launch is not preferred: weight gradient + data gradient as two launches
-        fused_dw = (FUSE_DW_BWD and a.expand != 1 and ops.dwconv_bwd_fused_ok(n, h, w, a.cexp, k, s, l, t, oh, ow, cin=a.cin if efree else 0))
-        assert fused_dw or not efree                         # (efree_ok asked the same question in the forward)
-        if not fused_dw:
-            dwdw = ops.dwconv_bwd_weight(dw_in, dd, n, h, w, a.cexp, k, s, l, t, oh, ow, pro=pro0)
+        if not pl.fused_dw:
+            dwdw = ops.dwconv_bwd_weight(dw_in, dd, *pl.dw, pro=pro0)
         grads = {}
         if a.expand != 1:
             # the data-gradient kernel finishes the bn0 + swish backward in its epilogue -- it reads e at the output
@@ -473,14 +436,13 @@ class _MBConvFn(torch.autograd.Function):
             # separate reduce pass over (e, dA0) is gone and the apply pass is a plain linear combination (stride 1: the
             # forward kernel on flipped taps; stride 2, round 3: the marching super-pixel kernel -- dA0 of the stride-2
             # blocks, the largest tensors of the network, is never written)
-            if fused_dw:
+            if pl.fused_dw:
                 dz0, part0, dwdw = ops.dwconv_bwd_fused(dd, e, st0, wflip, n, h, w, a.cexp, k, l, t, oh, ow,
-                                                        xw=(x, sv["we"]) if efree else None)
+                                                        xw=(x, sv["we"]) if pl.efree else None)
             else:
-                dz0, part0 = ops.dwconv_bwd_data(dd, sv["wkkc"], n, h, w, a.cexp, k, s, l, t, oh, ow, w_kkc_flipped=wflip,
-                                                 epi=(e, st0))
+                dz0, part0 = ops.dwconv_bwd_data(dd, sv["wkkc"], *pl.dw, w_kkc_flipped=wflip, epi=(e, st0))
             del dd
-            if efree or 2 * n * hw * a.cexp >= (BN_FOLD_MIN_BYTES if s == 1 else max(BN_FOLD_MIN_BYTES, BN_FOLD_S2_MIN_BYTES)):
+            if pl.fold_bn0:
                 # bn0 backward is linear in (dZ0, e) and e = x We^T: it is folded into the operands of the expand conv's
                 # two gradient GEMMs (ops.bn_fold_expand_bwd) -- de is never formed, e is not read again.  Three passes
                 # over the expanded tensor against ~10 small launches and 6 passes over the (6x smaller) block input:
@@ -489,7 +451,7 @@ class _MBConvFn(torch.autograd.Function):
                 del e, dw_in
                 coef0, dg0, db0 = ops.bn_bwd_coefs(part0, n * hw, st0, blk._bn0.weight)
                 dx, dwe = ops.bn_fold_expand_bwd(dz0, x, blk._expand_conv.weight.view(a.cexp, a.cin), sv["we"], coef0,
-                                                 db0, n * hw, residual=dy if a.skip else None, gram=sv.get("gram"))
+                                                 db0, n * hw, residual=dy if a.skip else None, gram=sv["gram"])
                 de = None
             else:
                 de, dg0, db0 = ops.bnact_bwd(e, n, hw, a.cexp, st0, blk._bn0.weight, 0, g=dz0, partials=part0)
@@ -498,16 +460,15 @@ class _MBConvFn(torch.autograd.Function):
         elif link is not None:
             # linked stem: this launch finishes the STEM's bn0 + swish backward (x is the stem's raw conv output): what goes
             # back is dZ0 = dL/d bn0(x), the BatchNorm reductions travel in the link
-            da0, link.part = ops.dwconv_bwd_data(dd, sv["wkkc"], n, h, w, a.cexp, k, s, l, t, oh, ow, w_kkc_flipped=wflip,
-                                                 epi=(x, link.st))
+            da0, link.part = ops.dwconv_bwd_data(dd, sv["wkkc"], *pl.dw, w_kkc_flipped=wflip, epi=(x, link.st))
             del dd
         else:
-            da0 = ops.dwconv_bwd_data(dd, sv["wkkc"], n, h, w, a.cexp, k, s, l, t, oh, ow, w_kkc_flipped=wflip)
+            da0 = ops.dwconv_bwd_data(dd, sv["wkkc"], *pl.dw, w_kkc_flipped=wflip)
             del dd
         if a.expand != 1:
             if de is not None:
-                we_t = ops.cast_transpose_bf16(blk._expand_conv.weight.view(a.cexp, a.cin))     # [cin, cexp]
-                if ops.xbwd_rows_ok(n * hw, a.cexp, a.cin):     # one pass over de for both gradients (round 5)
+                we_t = blk.w_expand(transposed=True)         # [cin, cexp]
+                if pl.xbwd:                                  # one pass over de for both gradients (round 5)
                     dx, dwe = ops.xbwd_rows(de, x, we_t, residual=dy if a.skip else None)
                 else:
                     dx = ops.linear_dgrad(de, sv["we"], residual=dy if a.skip else None, w_t=we_t)
@@ -525,7 +486,7 @@ class _MBConvFn(torch.autograd.Function):
         grads["_project_conv.weight"] = dwp.view(a.cout, a.cexp, 1, 1)
         grads["_bn2.weight"], grads["_bn2.bias"] = dg2, db2
         ctx.saved = None
-        return (dx, None, None, None, None, None) + ops.deliver_param_grads(blk._params(), [grads[nm] for nm in blk._param_names])
+        return (dx, None, None, None, None, None, None, None) + ops.deliver_param_grads(blk._params(), [grads[nm] for nm in blk._param_names])
 
 
 class _HeadFn(torch.autograd.Function):
@@ -600,6 +561,9 @@ class _Conv(nn.Conv2d):
 
 
 _Geo = namedtuple("_Geo", ["idx", "expand", "k", "s", "cin", "cexp", "cout", "cse", "pad", "skip"])
+# one call of an MBConv block (MBConvBlock.plan); dw = (n, h, w, cexp, k, s, pad_l, pad_t, oh, ow), the argument run of ops.dwconv_*
+_Plan = namedtuple("_Plan", ["n", "h", "w", "oh", "ow", "training", "xdw", "efree", "fp8_expand", "keep_act", "fp8_project",
+                             "store_e", "store_d", "store_p", "fuse_proj_dgrad", "fused_dw", "fold_bn0", "xbwd", "dw"])
 
 
 class MBConvBlock(nn.Module):
@@ -632,21 +596,68 @@ class MBConvBlock(nn.Module):
         self.register_buffer("_ones", torch.ones(cin), persistent=False)
         self.register_buffer("_zeros", torch.zeros(cin), persistent=False)
 
-    def xdw_ok(self, n, h, w, oh, ow):
-        """does this block's forward take the fused expand + depthwise launch (ops.mbconv_xdw_fwd) when its expanded tensor
-        need not be stored?"""
+    def out_geo(self, n, h, w):
+        """(n, oh, ow) of this block's output for an (n, h, w) input"""
         a = self.args
-        return (a.expand != 1 and a.cin <= XDW_MAX_CIN and not self.fp8
-                and ops.mbconv_xdw_ok(n, h, w, a.cin, a.cexp, a.k, a.s, a.pad[0], a.pad[2], oh, ow))
+        l, r, t, b = a.pad
+        return n, _out_extent(h, t, b, a.k, a.s), _out_extent(w, l, r, a.k, a.s)
 
-    def efree_ok(self, n, h, w, oh, ow):
-        """may this block's expanded tensor never exist -- fused forward, fused backward with the e rows formed from the block
-        input, folded BatchNorm0 backward?  (stride-1 3x3, at most 64 input channels, the shapes on which the fused backward
-        launch is the preferred form, and enough expanded bytes for the fold to be the chosen BatchNorm0 backward)"""
+    def xdw_capable(self):
+        """the shape-independent half of ``plan().xdw``: may the expand conv run inside the depthwise launch (ops.mbconv_xdw_fwd)?"""
         a = self.args
-        return bool(ops.EFREE and FUSE_DW_BWD and a.k == 3 and a.s == 1 and self.training and self.xdw_ok(n, h, w, oh, ow)
-                    and 2 * n * h * w * a.cexp >= BN_FOLD_MIN_BYTES
-                    and ops.dwconv_bwd_fused_ok(n, h, w, a.cexp, a.k, a.s, a.pad[0], a.pad[2], oh, ow, cin=a.cin))
+        return bool(ops.XDW) and a.expand != 1 and a.cin <= XDW_MAX_CIN and not self.fp8
+
+    def plan(self, n, h, w, recording):
+        """Every path choice of ONE call of this block on an (n, h, w) input, forward and backward, from the block's mode (training /
+        recompute / fp8), the module-level switches and thresholds as they stand NOW and the library's (cached) shape predicates.
+        ``_MBConvFn.forward`` stores the plan with the graph; the backward reads only that.
+
+        recording: is an autograd graph being recorded?  (autograd runs Function.forward with grad mode off and reports
+        needs_input_grad from requires_grad alone: ``forward`` passes ``torch.is_grad_enabled()``.)  A block that may store its
+        expanded tensor e runs the two-launch forward when recording (e rounded to 16 bits, stored), the fused one otherwise.
+        Grad mode is only a proxy for "e must be stored": under ``torch.utils.checkpoint`` (first pass under no_grad, recompute
+        with grad on) the two passes would take different forwards and differ in the last bits.  Such a caller first sets
+        recompute mode >= 1 on the ``xdw_capable`` blocks, as ``EfficientNet.xdw_reforward_modes`` does for the micro-batched step."""
+        a, rc, expand = self.args, self.recompute, self.args.expand != 1
+        _, oh, ow = self.out_geo(n, h, w)
+        rows, orows = n * h * w, n * oh * ow
+        dw = (n, h, w, a.cexp, a.k, a.s, a.pad[0], a.pad[2], oh, ow)
+        fusable = self.xdw_capable() and ops.mbconv_xdw_ok(n, h, w, a.cin, *dw[3:])
+        # stride-1 3x3 blocks whose backward forms its e rows from x as well (ops.dwconv_bwd_fused with xw) and folds the
+        # BatchNorm0 backward into the expand conv's gradient GEMMs never need e anywhere: an E-free plan IS fused forward +
+        # fused depthwise backward + fold (enough expanded bytes for the fold to be the chosen BatchNorm0 backward)
+        efree = bool(fusable and ops.EFREE and FUSE_DW_BWD and a.k == 3 and a.s == 1 and self.training
+                     and 2 * rows * a.cexp >= BN_FOLD_MIN_BYTES and ops.dwconv_bwd_fused_ok(*dw, cin=a.cin))
+        # ... and where no backward needs e stored (no graph, or a recompute mode that rebuilds it) the forward is fused too
+        xdw = efree or (fusable and (rc >= 1 or not recording))
+        keep_act = not ops._rows_ok(orows, a.cout, a.cexp, None, 0)
+        fold = fused_dw = fuse_proj = xbwd = False
+        if recording:
+            fuse_proj = bool(FUSE_PROJ_DGRAD and ops.proj_dgrad_fusable(orows, a.cexp, a.cout, oh * ow))
+            fused_dw = efree or bool(FUSE_DW_BWD and expand and ops.dwconv_bwd_fused_ok(*dw))
+            fold = expand and (efree or 2 * rows * a.cexp >= (BN_FOLD_MIN_BYTES if a.s == 1 else max(BN_FOLD_MIN_BYTES, BN_FOLD_S2_MIN_BYTES)))
+            xbwd = expand and not fold and ops.xbwd_rows_ok(rows, a.cexp, a.cin)
+        return _Plan(n, h, w, oh, ow, self.training, xdw, efree,
+                     fp8_expand=bool(expand and self.fp8 and a.cin % 16 == 0 and not ops._rows_ok(rows, a.cexp, a.cin, None, 0)),
+                     keep_act=keep_act, fp8_project=keep_act and self.fp8 and a.cexp % 16 == 0 and a.cout > 64,
+                     store_e=expand and rc == 0 and not xdw, store_d=rc < 2, store_p=rc < 4,
+                     fuse_proj_dgrad=fuse_proj, fused_dw=fused_dw, fold_bn0=fold, xbwd=xbwd, dw=dw)
+
+    def w_expand(self, transposed=False):
+        """cached 16-bit image of the expand conv's weight, [cexp, cin] or transposed.  (Forward, backward and
+        ``EfficientNet.warm_weight_images`` all ask w_*: the cache key holds pointer, shape and strides of the view)"""
+        v = self._expand_conv.weight.view(self.args.cexp, self.args.cin)
+        return ops.cast_transpose_bf16(v) if transposed else ops.cast_bf16(v)
+
+    def w_taps(self, flipped=False):
+        """cached fp32 depthwise taps [k*k, cexp], or rotated by 180 degrees (stride-1 data gradient)"""
+        v = self._depthwise_conv.weight.view(self.args.cexp, self.args.k * self.args.k)
+        return ops.flipped_taps_f32(v) if flipped else ops.transpose_f32(v, cache=True)
+
+    def w_project(self, transposed=False):
+        """cached 16-bit image of the project conv's weight: [cout, cexp], or transposed [cexp, cout] (backward)"""
+        v = self._project_conv.weight.view(self.args.cout, self.args.cexp)
+        return ops.cast_transpose_bf16(v) if transposed else ops.cast_bf16(v)
 
     def _params(self):
         """the block's Parameter objects in ``_param_names`` order (cached: ``named_parameters`` walks the module tree)"""
@@ -668,9 +679,9 @@ class MBConvBlock(nn.Module):
             self.__dict__["_plist"] = (ps, slots)
         return ps
 
-    def forward(self, inputs, n, h, w, rowscale=None):
-        self.__dict__["_recording"] = torch.is_grad_enabled()      # is an autograd graph being recorded for this call?
-        return _MBConvFn.apply(inputs, rowscale, self, n, h, w, *self._params())
+    def forward(self, inputs, n, h, w, rowscale=None, link=None):
+        """link: the ``_StemLink`` of a linked stem whose raw output this call reads (block 0); grad mode: see ``plan``"""
+        return _MBConvFn.apply(inputs, rowscale, self, n, h, w, torch.is_grad_enabled(), link, *self._params())
 
 
 class EfficientNet(nn.Module):
@@ -780,11 +791,8 @@ class EfficientNet(nn.Module):
         expanded tensor rebuilt by one GEMM in the backward) instead of the two-launch forward that rounds e to 16 bits first.
         Returns the list of (block, previous mode) to restore."""
         changed = []
-        if not ops.XDW:
-            return changed
         for blk in self._blocks:
-            a = blk.args
-            if blk.recompute == 0 and a.expand != 1 and a.cin <= XDW_MAX_CIN and not blk.fp8:
+            if blk.recompute == 0 and blk.xdw_capable():
                 changed.append((blk, blk.recompute))
                 blk.recompute = 1
         return changed
@@ -793,6 +801,20 @@ class EfficientNet(nn.Module):
         """No-op: the swish is always the fused, recompute-in-backward form."""
 
     # ---------------------------------------------------------------------------- forward
+    def stem_geo(self, n, h, w):
+        """(n, oh, ow) of the stem's output (= block 0's input) for n images of h x w"""
+        l, r, t, b = self.stem_pad
+        return n, _out_extent(h, t, b, 3, 2), _out_extent(w, l, r, 3, 2)
+
+    def _stem(self, x):
+        """stem of one chain -> (output, its _StemLink or None, output geometry).  Block 0 has no expand conv (every EfficientNet-
+        B*): the stem's bn0 + swish then runs inside block 0's depthwise kernels, which get the link with the stem's RAW output"""
+        b0 = self._blocks[0].args
+        link = _StemLink() if (LINK_STEM and b0.expand == 1 and not b0.skip and b0.s == 1) else None
+        args = (x, self._conv_stem.weight, self._bn0.weight, self._bn0.bias, self)
+        y = _StemFn.apply(*args, link) if link is not None else _StemFn.apply(*args)
+        return y, link, self.stem_geo(x.shape[0], *x.shape[2:])
+
     def _drop_connect_scales(self, n, device, seed):
         """keep/keep_prob per (block, sample) [ref: efficient_net_custom_utils.py:129-154]; rate = 0.2*idx/len."""
         rate = self._global_params.drop_connect_rate
@@ -819,19 +841,11 @@ class EfficientNet(nn.Module):
         for bn in bns:
             bn.defer_count = counters
         try:
-            b0 = self._blocks[0].args
-            # block 0 has no expand conv (every EfficientNet-B*): the stem's bn0 + swish runs inside its depthwise kernels
-            link = _StemLink() if (LINK_STEM and b0.expand == 1 and not b0.skip and b0.s == 1) else None
-            if link is not None:
-                y = _StemFn.apply(x, self._conv_stem.weight, self._bn0.weight, self._bn0.bias, self, link)
-                self._blocks[0].__dict__["_in_link"] = link
-            else:
-                y = _StemFn.apply(x, self._conv_stem.weight, self._bn0.weight, self._bn0.bias, self)
-            n, h, w = self._geo
+            y, link, (n, h, w) = self._stem(x)
             scales = self._drop_connect_scales(n, x.device, seed)
             for blk, rs in zip(self._blocks, scales):
-                y = blk(y, n, h, w, rs)
-                n, h, w = blk._out_geo
+                y = blk(y, n, h, w, rs, link if blk.args.idx == 0 else None)
+                n, h, w = blk.out_geo(n, h, w)
         finally:
             for bn in bns:
                 bn.defer_count = None
@@ -842,20 +856,19 @@ class EfficientNet(nn.Module):
     def warm_weight_images(self, backward: bool):
         """Build (or find) every cached weight image the forward -- and, with ``backward``, the backward -- of this encoder
         reads, on the CURRENT stream: two calls of the encoder on different streams then only ever hit the cache (an image
-        built by one chain while the other chain is in flight would be read without an ordering between the streams).  Same
-        helper calls with the same views as the autograd functions below (the cache key holds pointer, shape and strides)."""
+        built by one chain while the other chain is in flight would be read without an ordering between the streams).  The
+        blocks' images come from the accessors their autograd function uses (``MBConvBlock.w_*``)."""
         for blk in self._blocks:
-            a = blk.args
-            if a.expand != 1:
-                ops.cast_bf16(blk._expand_conv.weight.view(a.cexp, a.cin))
+            if blk.args.expand != 1:
+                blk.w_expand()
                 if backward:
-                    ops.cast_transpose_bf16(blk._expand_conv.weight.view(a.cexp, a.cin))
-            ops.transpose_f32(blk._depthwise_conv.weight.view(a.cexp, a.k * a.k), cache=True)
-            if backward and a.s == 1:
-                ops.flipped_taps_f32(blk._depthwise_conv.weight.view(a.cexp, a.k * a.k))
-            ops.cast_bf16(blk._project_conv.weight.view(a.cout, a.cexp))
+                    blk.w_expand(transposed=True)
+            blk.w_taps()
+            if backward and blk.args.s == 1:
+                blk.w_taps(flipped=True)
+            blk.w_project()
             if backward:
-                ops.cast_transpose_bf16(blk._project_conv.weight.view(a.cout, a.cexp))
+                blk.w_project(transposed=True)
         cout, cin = self._conv_head.weight.shape[0], self._conv_head.weight.shape[1]
         ops.cast_bf16(self._conv_head.weight.view(cout, cin))
         if backward:
@@ -915,32 +928,19 @@ class EfficientNet(nn.Module):
                 bn.defer_count = counters[i]
             _BN_DEFER = defer if i else None
 
-        b0 = self._blocks[0].args
-        linked = LINK_STEM and b0.expand == 1 and not b0.skip and b0.s == 1
-        ys, scales, geo = [None, None], [None, None], None
+        ys, scales, links = [None, None], [None, None], [None, None]
         try:
             torch.cuda.set_stream(side)
             defer = _BNDefer(self) if training else None          # (zero-filled scratch: allocated and cleared on the side stream)
-            links = [None, None]
             for i in (0, 1):
                 chain(i)
-                links[i] = _StemLink() if linked else None
-                if linked:
-                    ys[i] = _StemFn.apply(xs[i], self._conv_stem.weight, self._bn0.weight, self._bn0.bias, self, links[i])
-                else:
-                    ys[i] = _StemFn.apply(xs[i], self._conv_stem.weight, self._bn0.weight, self._bn0.bias, self)
-                n, h, w = self._geo
+                ys[i], links[i], (n, h, w) = self._stem(xs[i])
                 scales[i] = self._drop_connect_scales(n, xs[i].device, seeds[i])
-            geo = (n, h, w)
             for bi, blk in enumerate(self._blocks):
-                n, h, w = geo
                 for i in (0, 1):
                     chain(i)
-                    if bi == 0 and linked:
-                        blk.__dict__["_in_link"] = links[i]
-                    ys[i] = blk(ys[i], n, h, w, scales[i][bi])
-                geo = blk._out_geo
-            n, h, w = geo
+                    ys[i] = blk(ys[i], n, h, w, scales[i][bi], links[i] if bi == 0 else None)
+                n, h, w = blk.out_geo(n, h, w)
             pooled = [None, None]
             for i in (0, 1):
                 chain(i)

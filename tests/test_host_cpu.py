@@ -217,6 +217,78 @@ def test_round5_host_policies_of_the_library():
     assert lib.mc_gemm256_tn_splits(3072, 768, 16384, 0) == 7 and lib.mc_gemm256_tn_splits(768, 768, 16384, 0) == 24
 
 
+def _span(*ranges):
+    return [i for lo, hi in ranges for i in range(lo, hi + 1)]
+
+
+_PLAN_TABLE = [
+    ("efficientnet-b5", 32, 1520, 912, dict(xdw_ok=_span((3, 13)), efree=_span((4, 7)), fused_dw=_span((4, 7), (14, 19), (36, 38)),
+                                            fold_bn0=_span((3, 27), (37, 38)), no_keep_act=_span((0, 12)), fuse_proj_dgrad=_span((3, 7)))),
+    ("efficientnet-b2", 64, 912, 912, dict(xdw_ok=_span((2, 8)), efree=_span((3, 4)), fused_dw=_span((3, 4), (9, 11), (21, 22)),
+                                           fold_bn0=_span((2, 8), (13, 16)), no_keep_act=_span((0, 7)), fuse_proj_dgrad=_span((3, 4)))),
+]
+
+
+def test_mbconv_plan_of_every_block():
+    """MBConvBlock.plan (the one place where the forward / backward paths of a block call are chosen) needs no device: the
+    library's shape predicates are host functions.  Pinned per block (``blk.args.idx``) at the per-GPU batch of the timed
+    workloads, default switches and thresholds, bf16: a changed threshold or library predicate shows up HERE.  The lists are
+    what the separate forward / backward conditions of the code before ``plan`` gave at these shapes ("B5 blocks
+    4-7", "B2 blocks 3-4")."""
+    for name, n, H, W, want in _PLAN_TABLE:
+        _check_plans(name, n, H, W, want)
+
+
+def _check_plans(name, n, H, W, want):
+    from mammo_clip_amd.breastclip.model.modules.efficientnet_custom import EfficientNet
+    enc = EfficientNet.from_name(name).train()
+
+    def plans(recording):
+        out, geo = [], enc.stem_geo(n, H, W)
+        for blk in enc._blocks:
+            out.append(blk.plan(*geo, recording))
+            assert (out[-1].n, out[-1].oh, out[-1].ow) == blk.out_geo(*geo)
+            geo = blk.out_geo(*geo)
+        return out
+
+    def idx(ps, field, value=True):
+        return [i for i, p in enumerate(ps) if getattr(p, field) == value]
+
+    assert [blk.args.idx for blk in enc._blocks] == list(range(len(enc._blocks)))
+    has_expand = [blk.args.idx for blk in enc._blocks if blk.args.expand != 1]
+    # training, recompute 0, graph recorded: only the E-free blocks run the fused forward, every other block stores e
+    ps = plans(True)
+    assert idx(ps, "efree") == want["efree"] and idx(ps, "xdw") == want["efree"]
+    assert idx(ps, "fused_dw") == want["fused_dw"] and idx(ps, "fold_bn0") == want["fold_bn0"]
+    assert idx(ps, "keep_act", False) == want["no_keep_act"] and idx(ps, "fuse_proj_dgrad") == want["fuse_proj_dgrad"]
+    assert idx(ps, "store_e") == [i for i in has_expand if i not in want["efree"]]
+    assert all(p.store_d and p.store_p and not p.fp8_expand and not p.fp8_project and p.training for p in ps)
+    assert all(p.fused_dw and p.fold_bn0 for p in ps if p.efree) and not any(p.xbwd and p.fold_bn0 for p in ps)
+    # no graph: the whole eligible column runs the fused forward
+    ps = plans(False)
+    assert idx(ps, "xdw") == want["xdw_ok"] and idx(ps, "efree") == want["efree"]
+    # recompute modes (EfficientNet.set_recompute): 1 drops e, 2 also d, 4 also p; 3 = 2 on the stride-1 3x3 blocks with an
+    # expand conv, 1 elsewhere
+    for mode in (1, 2, 3, 4):
+        enc.set_recompute(mode)
+        ps = plans(True)
+        assert idx(ps, "xdw") == want["xdw_ok"] and idx(ps, "efree") == want["efree"] and idx(ps, "store_e") == []
+        mode2 = [b.args.idx for b in enc._blocks if b.args.k == 3 and b.args.s == 1 and b.args.expand != 1]
+        assert idx(ps, "store_d", False) == {1: [], 2: list(range(len(ps))), 3: mode2, 4: list(range(len(ps)))}[mode]
+        assert idx(ps, "store_p", False) == (list(range(len(ps))) if mode == 4 else [])
+    enc.set_recompute(0)
+    # fp8 operands: neither fused forward nor E-free
+    enc.set_fp8(True)
+    ps = plans(True)
+    assert idx(ps, "xdw") == [] and idx(ps, "efree") == []
+    enc.set_fp8(False)
+    # eval: no E-free block; the eligible column still runs the fused forward (nothing is stored)
+    enc.eval()
+    with torch.no_grad():
+        ps = plans(False)
+    assert idx(ps, "efree") == [] and idx(ps, "xdw") == want["xdw_ok"] and not any(p.training for p in ps)
+
+
 def test_no_cpu_fallback():
     """the product path refuses CPU tensors instead of silently computing somewhere else"""
     model = build_model(_cfg(), {"breast_clip": {}}, types.SimpleNamespace(vocab_size=28996))

@@ -78,7 +78,7 @@ def test_mbconv_kats_vs_reference():
         blk.eval()
         with torch.no_grad():
             y = blk(nhwc(x), b, H, W)
-        n2, oh, ow = blk._out_geo
+        n2, oh, ow = blk.out_geo(b, H, W)
         e_eval = relerr(nchw(y, b, oh, ow), z[f"{nme}/y_eval"])
         # train + backward
         blk.train()
