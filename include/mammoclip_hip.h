@@ -477,6 +477,60 @@ int mc_eos_gather(const mc_bf16* hid, const long long* mask, int b, int t, int h
 int mc_eos_scatter(const float* dout, const long long* mask, int b, int t, int h, mc_bf16* dhid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Packed (variable-length) text encoder: the b reports of a call as ONE [rows, h] matrix that holds only their real
+ * tokens.  Sequence i owns rows cu_seqlens[i] .. cu_seqlens[i+1]-1 (int32 [b+1], cu_seqlens[0] = 0); rows
+ * cu_seqlens[b] .. rows-1 are alignment rows that belong to no sequence; row_map[rows] (int32) is the row i*t_pad + position
+ * of each packed row in the padded [b, t_pad] layout (-1 for alignment rows).  The reference pads every report to
+ * max_length 256 and runs BertModel on all of them [ref: data/datasets/imagetext.py:217-222;
+ * model/modules/text_encoder.py:47-49]; the padded rows are never read by a real token, so leaving them out changes
+ * no result.  Every dropout mask below is the one the padded entry point draws for the same (seed, stream_id):
+ * the element index is formed from the padded row. */
+/* Fused self-attention on packed rows (attn_varlen.hip), head size 64, 1 <= len_i <= max_len <= 256:
+ *   ctx[rows, nh*64] = dropout(softmax(alpha * Q K^T)) V   per (sequence, head) over the sequence's own tokens
+ * -- mc_attn_fwd on the padded batch with a 1..10..0 mask, without the padded rows
+ * [ref: model/modules/text_encoder.py:47-49 -> transformers BertSelfAttention.forward].  qkv = [rows, 3*nh*64];
+ * lse = [rows, nh, 2]; order = int32 [b] sequence indices in launch order (longest first) or NULL; t_pad = T of the padded
+ * layout (multiple of 8, >= max_len).  Alignment rows of ctx / dqkv are written with zeros. */
+int mc_attn_varlen_supported(int max_len, int head_dim);
+int mc_attn_varlen_fwd(const mc_bf16* qkv, const int* cu_seqlens, const int* order, int b, int max_len, int t_pad,
+                       long long rows, int nh, float alpha, float p, unsigned long long seed, unsigned int stream_id,
+                       mc_bf16* ctx, float* lse, void* stream);
+int mc_attn_varlen_bwd(const mc_bf16* qkv, const int* cu_seqlens, const int* order, const mc_bf16* dctx, const float* lse,
+                       int b, int max_len, int t_pad, long long rows, int nh, float alpha, float p,
+                       unsigned long long seed, unsigned int stream_id, mc_bf16* dqkv, void* stream);
+/* mc_bert_embed_fwd / _bwd on packed rows [ref: transformers BertEmbeddings via text_encoder.py:47-49]: ids / tt in packed
+ * order, pos_ids[r] = r - cu_seqlens[i]; alignment rows of y are zeros.  The backward accumulates (+=) like the padded one. */
+int mc_bert_embed_rows_fwd(const long long* ids, const long long* tt, const int* pos_ids, const int* row_map,
+                           const float* word, const float* pos, const float* type, const float* gamma,
+                           const float* beta, float eps, long long rows, int h, float p, unsigned long long seed,
+                           unsigned int stream_id, mc_bf16* y, float* mean, float* rstd, void* stream);
+int mc_bert_embed_rows_bwd(const mc_bf16* dy, const long long* ids, const long long* tt, const int* cu_seqlens,
+                           const float* word, const float* pos, const float* type, const float* gamma,
+                           const float* mean, const float* rstd, int b, int max_len, int t_pad, int h, float p,
+                           unsigned long long seed, unsigned int stream_id, float* dword, float* dpos, float* dtype,
+                           float* dgamma, float* dbeta, void* stream);
+/* mc_add_ln_fwd / _bwd on packed rows [ref: transformers BertSelfOutput / BertOutput via text_encoder.py:47-49]; alignment
+ * rows are normalised without dropout (finite in, finite out). */
+int mc_add_ln_rows_fwd(const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma, const float* beta,
+                       float eps, long long rows, int h, float p, unsigned long long seed, unsigned int stream_id,
+                       mc_bf16* y, float* mean, float* rstd, void* stream);
+int mc_add_ln_rows_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma,
+                       const float* mean, const float* rstd, long long rows, int h, float p, unsigned long long seed,
+                       unsigned int stream_id, mc_bf16* dx, mc_bf16* dres, float* dgamma, float* dbeta, void* stream);
+/* Pooling from packed rows [ref: model/clip.py:65-75]: eos = gather of rows cu_seqlens[i+1]-1, bos = rows cu_seqlens[i]
+ * (out[i] = float(src[idx[i]]); the backward scatters into a zero-filled dsrc), mean = per-sequence mean. */
+int mc_rows_gather(const mc_bf16* src, const int* idx, int n, int h, float* out, void* stream);
+int mc_rows_scatter(const float* dout, const int* idx, int n, int h, mc_bf16* dsrc, void* stream);
+int mc_segment_mean_fwd(const mc_bf16* src, const int* cu_seqlens, int b, int h, float* out, void* stream);
+/* every row of dsrc written (alignment rows: zeros); t = t_pad of row_map */
+int mc_segment_mean_bwd(const float* dout, const int* cu_seqlens, const int* row_map, long long rows, int t, int h,
+                        mc_bf16* dsrc, void* stream);
+/* last_hidden_state [b, t, h] from packed rows, zeros at the padded positions [ref: text_encoder.py:49], and its backward
+ * (gather of the real rows, zeros in the alignment rows); h % 8 == 0 */
+int mc_unpack_rows(const mc_bf16* src, const int* cu_seqlens, int b, int t, int h, mc_bf16* dst, void* stream);
+int mc_pack_rows(const mc_bf16* src, const int* row_map, long long rows, int h, mc_bf16* dst, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * fp32 small GEMM with arbitrary strides: C[m,n] = alpha * sum_k A[m*ars + k*acs] * B[k*brs + n*bcs] + beta*C + bias[n]
  * [ref: model/modules/projection.py:23-29 (LinearProjectionHead); loss/breast_clip.py:46-100 (logits)] */
 /* alpha_dev (optional): device scalar multiplied into alpha (e.g. the learnable logit scale).

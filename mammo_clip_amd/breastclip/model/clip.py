@@ -33,6 +33,44 @@ class _EosPoolFn(torch.autograd.Function):
         return ops.eos_scatter(dout.contiguous(), mask, b, t, h).view(b, t, h), None
 
 
+class _PackedRowPoolFn(torch.autograd.Function):
+    """features[i] = rows[idx[i]] of a packed text batch: eos pooling with idx = cu_seqlens[i+1]-1, bos with idx =
+    cu_seqlens[i]  [ref: clip.py:65-70]; backward: scatter into zeros"""
+
+    @staticmethod
+    def forward(ctx, rows, idx):
+        ctx.n = rows.shape[0]
+        ctx.save_for_backward(idx)
+        return ops.rows_gather(rows.contiguous(), idx)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (idx,) = ctx.saved_tensors
+        return ops.rows_scatter(dout.contiguous(), idx, ctx.n), None
+
+
+class _PackedMeanPoolFn(torch.autograd.Function):
+    """features[i] = mean of the rows of sequence i of a packed text batch  [ref: clip.py:71-75]"""
+
+    @staticmethod
+    def forward(ctx, rows, pk):
+        ctx.pk = pk
+        return ops.segment_mean_fwd(rows.contiguous(), pk)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ops.segment_mean_bwd(dout.contiguous(), ctx.pk), None
+
+
+def _with_host_lengths(tokens):
+    """packed text mode: the prefix lengths of an attention mask that is still on the HOST ride along as ``seq_lengths`` (a
+    host tensor), so the encoder sizes its packed batch without reading anything back from the device"""
+    mask = tokens.get("attention_mask") if hasattr(tokens, "get") else None
+    if not torch.is_tensor(mask) or mask.is_cuda or mask.dim() != 2:
+        return None
+    return ops.prefix_lengths(mask)
+
+
 class _L2NormFn(torch.autograd.Function):
     """x / ||x||_2 per row, no epsilon [ref: clip.py:90-91]"""
 
@@ -98,7 +136,20 @@ class BreastClip(nn.Module):
         return _L2NormFn.apply(emb)
 
     def encode_text(self, text_tokens):
-        hid = self.text_encoder(text_tokens)
+        if getattr(self.text_encoder, "packed", False):
+            # packed mode: pool straight from the packed rows, [b, T, H] is never formed; a call that took the padded path
+            # (full masks, a mask with a hole) comes back as the usual hidden state
+            hid, pk = self.text_encoder.forward_packed(text_tokens)
+            if pk is not None:
+                if self.text_pooling == "eos":
+                    return _PackedRowPoolFn.apply(hid, pk.eos)
+                if self.text_pooling == "bos":
+                    return _PackedRowPoolFn.apply(hid, pk.cu[:pk.b])
+                if self.text_pooling == "mean":
+                    return _PackedMeanPoolFn.apply(hid, pk)
+                raise NotImplementedError("Not supported pooling method : %s", self.text_pooling)
+        else:
+            hid = self.text_encoder(text_tokens)
         if self.text_pooling == "eos":
             return _EosPoolFn.apply(hid, text_tokens["attention_mask"])
         if self.text_pooling == "bos":
@@ -156,7 +207,7 @@ class BreastClip(nn.Module):
                 main.wait_stream(s_view)
                 enc.side_call_end()
             view.record_stream(main)
-        tok = _tokens.to_device(batch["text_tokens"], device)
+        tok = self._tokens_to_device(batch["text_tokens"], device)
         txt2 = None
         if s_txt is not None:
             # token tensors moved to the device just now are main-stream allocations read by the text chain: ordered behind
@@ -178,6 +229,14 @@ class BreastClip(nn.Module):
                     t_.record_stream(main)
         return self._finish(batch, device, img, txt, txt2, two, view)
 
+    def _tokens_to_device(self, tokens, device):
+        lengths = _with_host_lengths(tokens) if getattr(self.text_encoder, "packed", False) else None
+        tok = _tokens.to_device(tokens, device)
+        if lengths is not None:
+            tok = dict(tok)
+            tok["seq_lengths"] = lengths
+        return tok
+
     def _encode_reports(self, batch, tok, two, device):
         txt2 = None
         if two:
@@ -185,7 +244,7 @@ class BreastClip(nn.Module):
             # shape: BERT has no cross-sample interaction (LayerNorm per token, attention per sequence), so the result
             # equals two calls [ref: clip.py:92,103 calls encode_text twice] while every GEMM sees twice the rows, the
             # weight gradients are produced once and ~360 launches per step disappear.
-            tok2 = _tokens.to_device(batch["text_tokens2"], device)
+            tok2 = self._tokens_to_device(batch["text_tokens2"], device)
             if _TEXT_ONE_CALL and tok.keys() == tok2.keys() and all(torch.is_tensor(tok[k]) and tok[k].shape == tok2[k].shape for k in tok):
                 nb = tok["input_ids"].shape[0]
                 both = self.encode_text({k: torch.cat([tok[k], tok2[k]]) for k in tok})
@@ -195,7 +254,7 @@ class BreastClip(nn.Module):
         else:
             txt = self.encode_text(tok)
         if two and txt2 is None:
-            txt2 = self.encode_text(_tokens.to_device(batch["text_tokens2"], device))
+            txt2 = self.encode_text(self._tokens_to_device(batch["text_tokens2"], device))
         return txt, txt2
 
     def _finish(self, batch, device, img, txt, txt2, two, view=None):

@@ -28,12 +28,15 @@ def load_image_encoder(config_image_encoder: Dict):
 
 def load_text_encoder(config_text_encoder: Dict, vocab_size: int):
     if config_text_encoder["source"].lower() == "huggingface":
-        return HuggingfaceTextEncoder(
+        enc = HuggingfaceTextEncoder(
             name=config_text_encoder["name"], vocab_size=vocab_size, pretrained=config_text_encoder["pretrained"],
             gradient_checkpointing=config_text_encoder.get("gradient_checkpointing", False),
             cache_dir=config_text_encoder.get("cache_dir", ""),
             trust_remote_code=config_text_encoder.get("trust_remote_code", False),
             config=config_text_encoder.get("config"))
+        # extension key: packed mode -- no work on the padded tokens of a report (BertModelHIP.set_packed); absent = off
+        enc.set_packed(bool(config_text_encoder.get("packed", False)))
+        return enc
     raise KeyError(f"Not supported text encoder: {config_text_encoder}")
 
 

@@ -50,14 +50,50 @@ class _EmbedFn(torch.autograd.Function):
         return ops.deliver_param_grads(ctx.params, (dword, dpos, dtyp, dgamma, dbeta)) + (None,) * 6
 
 
-class _LayerFn(torch.autograd.Function):
-    """One BertLayer: self-attention + output LayerNorm + FFN + output LayerNorm, forward and backward."""
+class _EmbedPackedFn(torch.autograd.Function):
+    """_EmbedFn on packed rows: ``ids`` / ``tt`` hold the real tokens in packed order (ops.PackedRows)."""
 
     @staticmethod
-    def forward(ctx, x, maskb, lyr, b, t, seed, *params):
+    def forward(ctx, word, pos, typ, gamma, beta, ids, tt, pk, eps, p, seed, sid):
+        y, mean, rstd = ops.bert_embed_rows_fwd(ids, tt, pk, word, pos, typ, gamma, beta, eps, p, seed, sid)
+        ctx.cfg = (pk, p, seed, sid)
+        ctx.params = (word, pos, typ, gamma, beta)
+        ctx.save_for_backward(word, pos, typ, gamma, ids, tt, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        word, pos, typ, gamma, ids, tt, mean, rstd = ctx.saved_tensors
+        pk, p, seed, sid = ctx.cfg
+        dword, dpos, dtyp, dgamma, dbeta = ops.bert_embed_rows_bwd(dy.contiguous(), ids, tt, pk, word, pos, typ, gamma, mean,
+                                                                   rstd, p, seed, sid)
+        dword[0].zero_()       # nn.Embedding(padding_idx=0), as in _EmbedFn
+        return ops.deliver_param_grads(ctx.params, (dword, dpos, dtyp, dgamma, dbeta)) + (None,) * 7
+
+
+class _UnpackFn(torch.autograd.Function):
+    """packed rows [R, H] -> [b*t, H] with zeros at the padded positions; backward: gather of the real rows"""
+
+    @staticmethod
+    def forward(ctx, x, pk):
+        ctx.pk = pk
+        return ops.unpack_rows(x, pk, pk.t)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.pack_rows(dy.contiguous(), ctx.pk.row_map), None
+
+
+class _LayerFn(torch.autograd.Function):
+    """One BertLayer: self-attention + output LayerNorm + FFN + output LayerNorm, forward and backward.
+    ``pk`` (ops.PackedRows) set: ``x`` holds packed rows -- every GEMM / GELU / column sum runs on pk.rows rows, attention
+    per sequence on its own length, and the LayerNorm kernels take the dropout indices of the padded layout from pk.row_map."""
+
+    @staticmethod
+    def forward(ctx, x, maskb, lyr, b, t, seed, pk, *params):
         att, H, nh = lyr.attention, lyr.hidden, lyr.heads
         hd = H // nh
-        M = b * t
+        M = b * t if pk is None else pk.rows
         pa, ph = (lyr.p_attn, lyr.p_hidden) if lyr.training else (0.0, 0.0)
         sid = 16 * lyr.index
         sq, sk, sv = att.self.query, att.self.key, att.self.value
@@ -89,8 +125,12 @@ class _LayerFn(torch.autograd.Function):
                 y_ = ops.linear_fwd(inp, w_lo if w_lo is not None else ops.cast_bf16_lo(w_src), residual=y_)
             return y_
         qkv = lin(x, wqkv, bqkv, None, wqkv_lo)
-        fused = ops.attn_supported(t, hd)
-        if fused:
+        if pk is not None:
+            if not ops.attn_varlen_supported(pk.max_len, hd):
+                raise RuntimeError(f"packed text encoder: no variable-length attention kernel for head size {hd}, length {pk.max_len}")
+            ctxv, lse = ops.attn_varlen_fwd(qkv, pk, nh, hd ** -0.5, pa, seed, sid)
+            probs = pd = None
+        elif ops.attn_supported(t, hd):
             # one kernel: scores, mask, softmax, dropout and context; only (row max, 1/row sum) are kept for backward
             ctxv, lse = ops.attn_fwd(qkv, maskb, b, t, nh, hd ** -0.5, pa, seed, sid)
             probs = pd = None
@@ -107,16 +147,20 @@ class _LayerFn(torch.autograd.Function):
                      sA=(nh * t * t, t * t), sB=(t * 3 * H, hd), sC=(t * H, hd))
         wo = ops.cast_bf16(att.output.dense.weight)
         ao = lin(ctxv, wo, att.output.dense.bias, att.output.dense.weight)
-        a, mean1, rstd1 = ops.add_ln_fwd(ao, x, att.output.LayerNorm.weight, att.output.LayerNorm.bias, lyr.eps, ph, seed,
-                                         sid + 1)
+        if pk is None:
+            def add_ln(u, r, ln, s_):
+                return ops.add_ln_fwd(u, r, ln.weight, ln.bias, lyr.eps, ph, seed, s_)
+        else:
+            def add_ln(u, r, ln, s_):
+                return ops.add_ln_rows_fwd(u, r, pk.row_map, ln.weight, ln.bias, lyr.eps, ph, seed, s_)
+        a, mean1, rstd1 = add_ln(ao, x, att.output.LayerNorm, sid + 1)
         wi = ops.cast_bf16(lyr.intermediate.dense.weight)
         h1 = lin(a, wi, lyr.intermediate.dense.bias, lyr.intermediate.dense.weight)
         hg = ops.gelu_fwd(h1)
         w2 = ops.cast_bf16(lyr.output.dense.weight)
         o = lin(hg, w2, lyr.output.dense.bias, lyr.output.dense.weight)
-        y, mean2, rstd2 = ops.add_ln_fwd(o, a, lyr.output.LayerNorm.weight, lyr.output.LayerNorm.bias, lyr.eps, ph, seed,
-                                         sid + 2)
-        ctx.lyr, ctx.cfg = lyr, (b, t, seed, pa, ph, sid)
+        y, mean2, rstd2 = add_ln(o, a, lyr.output.LayerNorm, sid + 2)
+        ctx.lyr, ctx.cfg, ctx.pk = lyr, (b, t, seed, pa, ph, sid), pk
         # hg = gelu(h1) is kept for the FFN2 weight gradient (100 MB per layer at 16384 rows: memory is not the constraint
         # of the text side, a recomputing GELU pass per layer and backward was)
         ctx.sv = dict(x=x, qkv=qkv, probs=probs, pd=pd, lse=lse, maskb=maskb, ctxv=ctxv, ao=ao, a=a, h1=h1, hg=hg, o=o, wqkv=wqkv, wo=wo, wi=wi, w2=w2,
@@ -133,8 +177,14 @@ class _LayerFn(torch.autograd.Function):
         x, qkv, probs, pd, a = sv["x"], sv["qkv"], sv["probs"], sv["pd"], sv["a"]
         dy = dy.contiguous()
         g = {}
+        pk = ctx.pk
+        if pk is None:
+            add_ln_bwd = ops.add_ln_bwd
+        else:
+            def add_ln_bwd(dy_, u, r, gamma, mean, rstd, p_, seed_, s_):
+                return ops.add_ln_rows_bwd(dy_, u, r, pk.row_map, gamma, mean, rstd, p_, seed_, s_)
         # y = LN2(dropout(o) + a)
-        do, da_res, g["output.LayerNorm.weight"], g["output.LayerNorm.bias"] = ops.add_ln_bwd(
+        do, da_res, g["output.LayerNorm.weight"], g["output.LayerNorm.bias"] = add_ln_bwd(
             dy, sv["o"], a, lyr.output.LayerNorm.weight, sv["ln2"][0], sv["ln2"][1], ph, seed, sid + 2)
         hg = sv.pop("hg")
         g["output.dense.weight"] = ops.linear_wgrad(do, hg)
@@ -148,14 +198,16 @@ class _LayerFn(torch.autograd.Function):
         da = ops.linear_dgrad(dh1, sv["wi"], residual=da_res, w_t=ops.cast_transpose_bf16(lyr.intermediate.dense.weight))
         del dh1, da_res
         # a = LN1(dropout(ao) + x)
-        dao, dx_res, g["attention.output.LayerNorm.weight"], g["attention.output.LayerNorm.bias"] = ops.add_ln_bwd(
+        dao, dx_res, g["attention.output.LayerNorm.weight"], g["attention.output.LayerNorm.bias"] = add_ln_bwd(
             da, sv["ao"], x, att.output.LayerNorm.weight, sv["ln1"][0], sv["ln1"][1], ph, seed, sid + 1)
         g["attention.output.dense.weight"] = ops.linear_wgrad(dao, sv["ctxv"])
         g["attention.output.dense.bias"] = ops.colsum(dao)
         dctx = ops.linear_dgrad(dao, sv["wo"], w_t=ops.cast_transpose_bf16(att.output.dense.weight))
         del dao
         # attention core
-        if sv["lse"] is not None:
+        if pk is not None:
+            dqkv = ops.attn_varlen_bwd(qkv, pk, dctx, sv["lse"], nh, hd ** -0.5, pa, seed, sid)
+        elif sv["lse"] is not None:
             dqkv = ops.attn_bwd(qkv, sv["maskb"], dctx, sv["lse"], b, t, nh, hd ** -0.5, pa, seed, sid)
         else:
             dpd = torch.empty((b, nh, t, t), dtype=torch.float32, device=x.device)
@@ -185,7 +237,7 @@ class _LayerFn(torch.autograd.Function):
             g[f"attention.self.{nm}.weight"] = dwqkv[i * H:(i + 1) * H]
             g[f"attention.self.{nm}.bias"] = dbqkv[i * H:(i + 1) * H]
         ctx.sv = None
-        return (dx, None, None, None, None, None) + ops.deliver_param_grads(lyr._params(), [g[nm] for nm in lyr._param_names])
+        return (dx, None, None, None, None, None, None) + ops.deliver_param_grads(lyr._params(), [g[nm] for nm in lyr._param_names])
 
 
 # ---------------------------------------------------------------------------------------------- containers
@@ -253,8 +305,8 @@ class BertLayerHIP(nn.Module):
             self.__dict__["_plist"] = (ps, slots)
         return ps
 
-    def forward(self, x, maskb, b, t, seed):
-        return _LayerFn.apply(x, maskb, self, b, t, seed, *self._params())
+    def forward(self, x, maskb, b, t, seed, pk=None):
+        return _LayerFn.apply(x, maskb, self, b, t, seed, pk, *self._params())
 
 
 class _Embeddings(nn.Module):
@@ -297,6 +349,32 @@ class BertModelHIP(nn.Module):
                     nn.init.zeros_(m.bias)
         self._calls = 0
         self.rng_seed = 0xBE27
+        self.packed = False
+
+    def set_packed(self, on: bool = True):
+        """Opt-in packed mode: a call whose attention masks are contiguous prefixes (1..10..0, what the tokenizer produces
+        with padding="max_length") runs on the real tokens only -- the b reports concatenated into one [sum(len), H] row
+        matrix (ops.PackedRows), attention per sequence on its own length (mc_attn_varlen_*).  BERT couples tokens only through
+        attention and a padded key has probability exactly 0, so the real tokens' outputs, the loss and every gradient are
+        those of the padded path; dropout draws the padded path's masks (same seeds, element indices of the padded layout).
+        ``last_hidden_state`` then holds ZEROS at the padded positions (the padded path, like the reference, leaves
+        unspecified finite values there that nothing reads).  A call with a hole in a mask, an all-zero row or only full
+        masks runs the padded launches.  Default off."""
+        self.packed = bool(on)
+        return self
+
+    def _packed_plan(self, attention_mask, seq_lengths, t0, device):
+        """ops.PackedRows of this call, or None when it takes the padded path.  ``seq_lengths``: ops.prefix_lengths of the mask
+        as a HOST tensor when the caller had the mask on the host (no synchronisation at all); otherwise the lengths are read
+        back from the device mask here -- the one device-to-host copy of a packed call."""
+        if not self.packed or attention_mask is None:
+            return None
+        if seq_lengths is None:
+            seq_lengths = ops.prefix_lengths(attention_mask)
+        lengths = seq_lengths.tolist()
+        if len(lengths) != attention_mask.shape[0] or not ops.packable(lengths, t0):
+            return None
+        return ops.PackedRows(lengths, t0).to(device)
 
     def set_hilo_weights(self, on: bool = True):
         """Opt-in precision mode of the encoder's linear layers: every weight matrix enters its MFMA GEMM as TWO bf16 operands
@@ -309,10 +387,15 @@ class BertModelHIP(nn.Module):
             lyr.hilo = bool(on)
         return self
 
-    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, **_):
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, seq_lengths=None, return_packed=False, **_):
+        """``seq_lengths`` (optional, packed mode): ops.prefix_lengths(attention_mask) taken on the host.  ``return_packed``:
+        a call that ran packed returns ``{"packed_rows": [R, H], "packed": ops.PackedRows}`` instead of forming [b, T, H]."""
         if not input_ids.is_cuda:
             raise RuntimeError("mammo_clip_amd.BertModelHIP runs only on a HIP device (no CPU fallback)")
         b, t0 = input_ids.shape
+        pk = self._packed_plan(attention_mask, seq_lengths, t0, input_ids.device)
+        if pk is not None:
+            return self._forward_packed(input_ids, token_type_ids, pk, return_packed)
         t = t0
         if t % 8:
             # the GEMM / softmax kernels want rows of 16 bytes: pad the sequences with masked [PAD] tokens (they are never
@@ -340,6 +423,23 @@ class BertModelHIP(nn.Module):
         return {"last_hidden_state": x if t == t0 else x[:, :t0].contiguous()}
 
 
+    def _forward_packed(self, input_ids, token_type_ids, pk, return_packed):
+        self._calls += 1                                   # the padded path's seed sequence
+        seed = self.rng_seed * 1000003 + self._calls
+        cfg, emb = self.config, self.embeddings
+        ids = torch.index_select(input_ids.reshape(-1), 0, pk.src)
+        tt = torch.index_select(token_type_ids.reshape(-1), 0, pk.src) if token_type_ids is not None else None
+        p = cfg.hidden_dropout_prob if self.training else 0.0
+        x = _EmbedPackedFn.apply(emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
+                                 emb.LayerNorm.weight, emb.LayerNorm.bias, ids, tt, pk, cfg.layer_norm_eps, p, seed, 15)
+        for lyr in self.encoder.layer:
+            x = lyr(x, None, pk.b, pk.t, seed, pk)
+        if return_packed:
+            return {"packed_rows": x, "packed": pk}
+        x = _UnpackFn.apply(x, pk).view(pk.b, pk.t, cfg.hidden_size)
+        return {"last_hidden_state": x if pk.t == pk.t0 else x[:, :pk.t0].contiguous()}
+
+
 class HuggingfaceTextEncoder(nn.Module):
     """[ref: model/modules/text_encoder.py:5-49]"""
 
@@ -352,6 +452,23 @@ class HuggingfaceTextEncoder(nn.Module):
         self.text_encoder = BertModelHIP(BertConfigLite(**(config or {})))
         self.name, self.pretrained = name, pretrained
         self.out_dim = self.text_encoder.config.hidden_size
+
+    @property
+    def packed(self):
+        return self.text_encoder.packed
+
+    def set_packed(self, on: bool = True):
+        """BertModelHIP.set_packed: skip the padded report tokens (default off; config key model.text_encoder.packed)"""
+        self.text_encoder.set_packed(on)
+        return self
+
+    def forward_packed(self, x):
+        """``(rows [R, H], ops.PackedRows)`` when the call ran packed, ``(last_hidden_state, None)`` when it took the padded
+        path -- one encoder call either way (BreastClip.encode_text pools straight from the packed rows)."""
+        out = self.text_encoder(**x, return_packed=True)
+        if "packed" in out:
+            return out["packed_rows"], out["packed"]
+        return out["last_hidden_state"], None
 
     def set_hilo_weights(self, on: bool = True):
         self.text_encoder.set_hilo_weights(on)

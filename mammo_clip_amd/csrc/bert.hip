@@ -31,7 +31,11 @@ __device__ __forceinline__ void ln_stats(const float (*x)[8], int nvec, int lane
     *rstd = rsqrtf(v + eps);
 }
 
+// MAP: packed rows -- ids / tt are in packed order, the position comes from pos_ids[row] and the dropout element index from
+// row_map[row] (the row of the padded [b, t] layout); a row with row_map < 0 belongs to no sequence and gets zeros
+template <bool MAP>
 __global__ __launch_bounds__(256) void embed_fwd_k(const long long* __restrict__ ids, const long long* __restrict__ tt,
+                                                   const int* __restrict__ pos_ids, const int* __restrict__ row_map,
                                                    const float* __restrict__ word, const float* __restrict__ pos,
                                                    const float* __restrict__ type, const float* __restrict__ gamma,
                                                    const float* __restrict__ beta, float eps, long long rows, int t,
@@ -41,9 +45,15 @@ __global__ __launch_bounds__(256) void embed_fwd_k(const long long* __restrict__
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nvec = h / 8;
     for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += (long long)gridDim.x * 4) {
+        const long long drow = MAP ? (long long)row_map[row] : row;
+        if (MAP && drow < 0) {
+            if (lane == 0) { mean[row] = 0.f; rstd[row] = 0.f; }
+            for (int v = lane; v < nvec; v += 64) *reinterpret_cast<uint4*>(y + row * h + v * 8) = make_uint4(0u, 0u, 0u, 0u);
+            continue;
+        }
         const long long id = ids[row];
         const long long ty = tt ? tt[row] : 0;
-        const int tp = (int)(row % t);
+        const int tp = MAP ? pos_ids[row] : (int)(row % t);
         float x[MAXV][8];
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) {
@@ -70,7 +80,7 @@ __global__ __launch_bounds__(256) void embed_fwd_k(const long long* __restrict__
 #pragma unroll
                 for (int q = 0; q < 8; ++q) o[q] = (x[i][q] - m) * rs * g[q] + b[q];
                 if (p > 0.f) {
-                    dropout_scale8(seed, sid, (unsigned long long)(row * nvec + v), p, ds);
+                    dropout_scale8(seed, sid, (unsigned long long)(drow * nvec + v), p, ds);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) o[q] *= ds[q];
                 }
@@ -81,7 +91,11 @@ __global__ __launch_bounds__(256) void embed_fwd_k(const long long* __restrict__
 }
 
 // wave w owns position tp = w % t and batch rows bi = w / t, w / t + nbw, ...
+// MAP: packed rows -- sequence bi owns rows cu[bi] .. cu[bi+1]-1 of dy / ids / tt / mean / rstd, t is the longest
+// sequence and tdrop the T of the padded layout (dropout element index)
+template <bool MAP>
 __global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy, const long long* __restrict__ ids,
+                                                   const int* __restrict__ cu, int tdrop,
                                                    const long long* __restrict__ tt, const float* __restrict__ word,
                                                    const float* __restrict__ pos, const float* __restrict__ type,
                                                    const float* __restrict__ gamma, const float* __restrict__ mean,
@@ -104,7 +118,9 @@ __global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy
         if (v < nvec) load8f(gamma + v * 8, g[i]);
     }
     for (int bi = bg; bi < b; bi += nbw) {
-        const long long row = (long long)bi * t + tp;
+        if (MAP && tp >= cu[bi + 1] - cu[bi]) continue;
+        const long long row = MAP ? (long long)cu[bi] + tp : (long long)bi * t + tp;
+        const long long drow = MAP ? (long long)bi * tdrop + tp : row;
         const long long id = ids[row];
         const long long ty = tt ? tt[row] : 0;
         const float m = mean[row], rs = rstd[row];
@@ -121,7 +137,7 @@ __global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy
                 unpack8(*reinterpret_cast<const uint4*>(dy + row * h + v * 8), d);
                 if (p > 0.f) {
                     float ds[8];
-                    dropout_scale8(seed, sid, (unsigned long long)(row * nvec + v), p, ds);
+                    dropout_scale8(seed, sid, (unsigned long long)(drow * nvec + v), p, ds);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) d[q] *= ds[q];
                 }
@@ -170,7 +186,11 @@ __global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy
     }
 }
 
+// MAP (add_ln_fwd_k / add_ln_bwd_k): packed rows -- the dropout element index comes from row_map[row], the row of the
+// padded [b, t] layout; a row with row_map < 0 belongs to no sequence and is not dropped
+template <bool MAP>
 __global__ __launch_bounds__(256) void add_ln_fwd_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ res,
+                                                    const int* __restrict__ row_map,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     float eps, long long rows, int h, float p, unsigned long long seed,
                                                     unsigned int sid, bf16_t* __restrict__ y, float* __restrict__ mean,
@@ -178,6 +198,7 @@ __global__ __launch_bounds__(256) void add_ln_fwd_k(const bf16_t* __restrict__ x
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nvec = h / 8;
     for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += (long long)gridDim.x * 4) {
+        const long long drow = MAP ? (long long)row_map[row] : row;
         float s[MAXV][8];
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) {
@@ -186,9 +207,9 @@ __global__ __launch_bounds__(256) void add_ln_fwd_k(const bf16_t* __restrict__ x
                 float a[8], r[8];
                 unpack8(*reinterpret_cast<const uint4*>(x + row * h + v * 8), a);
                 unpack8(*reinterpret_cast<const uint4*>(res + row * h + v * 8), r);
-                if (p > 0.f) {
+                if (p > 0.f && drow >= 0) {
                     float ds[8];
-                    dropout_scale8(seed, sid, (unsigned long long)(row * nvec + v), p, ds);
+                    dropout_scale8(seed, sid, (unsigned long long)(drow * nvec + v), p, ds);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) a[q] *= ds[q];
                 }
@@ -214,8 +235,10 @@ __global__ __launch_bounds__(256) void add_ln_fwd_k(const bf16_t* __restrict__ x
     }
 }
 
+template <bool MAP>
 __global__ __launch_bounds__(256) void add_ln_bwd_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
-                                                    const bf16_t* __restrict__ res, const float* __restrict__ gamma,
+                                                    const bf16_t* __restrict__ res, const int* __restrict__ row_map,
+                                                    const float* __restrict__ gamma,
                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
                                                     long long rows, int h, float p, unsigned long long seed,
                                                     unsigned int sid, bf16_t* __restrict__ dx, bf16_t* __restrict__ dres,
@@ -232,6 +255,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_k(const bf16_t* __restrict__ d
     }
     for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += (long long)gridDim.x * 4) {
         const float m = mean[row], rs = rstd[row];
+        const long long drow = MAP ? (long long)row_map[row] : row;
         float xh[MAXV][8], dg[MAXV][8], ds[MAXV][8];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -244,7 +268,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_k(const bf16_t* __restrict__ d
                 unpack8(*reinterpret_cast<const uint4*>(x + row * h + v * 8), a);
                 unpack8(*reinterpret_cast<const uint4*>(res + row * h + v * 8), r);
                 unpack8(*reinterpret_cast<const uint4*>(dy + row * h + v * 8), d);
-                if (p > 0.f) dropout_scale8(seed, sid, (unsigned long long)(row * nvec + v), p, ds[i]);
+                if (p > 0.f && drow >= 0) dropout_scale8(seed, sid, (unsigned long long)(drow * nvec + v), p, ds[i]);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     float xv = (a[q] * ds[i][q] + r[q] - m) * rs;
@@ -523,8 +547,8 @@ extern "C" int mc_bert_embed_fwd(const long long* ids, const long long* tt, cons
     MC_CHECK(ids && word && pos && type && gamma && beta && y && mean && rstd, "embed_fwd: null arg");
     MC_CHECK(b > 0 && t > 0 && h > 0 && h % 8 == 0 && h <= 1024, "embed_fwd: hidden must be a multiple of 8 and <= 1024");
     long long rows = (long long)b * t;
-    hipLaunchKernelGGL(embed_fwd_k, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, ids, tt, word, pos, type,
-                       gamma, beta, eps, rows, t, h, p, seed, stream_id, y, mean, rstd);
+    hipLaunchKernelGGL(embed_fwd_k<false>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, ids, tt, nullptr, nullptr,
+                       word, pos, type, gamma, beta, eps, rows, t, h, p, seed, stream_id, y, mean, rstd);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -539,8 +563,8 @@ extern "C" int mc_bert_embed_bwd(const mc_bf16* dy, const long long* ids, const 
     if (nbw < 1) nbw = 1;
     if (nbw > b) nbw = b;
     long long waves = (long long)t * nbw;
-    hipLaunchKernelGGL(embed_bwd_k, dim3(mc_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream, dy, ids, tt, word, pos,
-                       type, gamma, mean, rstd, b, t, h, nbw, p, seed, stream_id, dword, dpos, dtype, dgamma, dbeta);
+    hipLaunchKernelGGL(embed_bwd_k<false>, dim3(mc_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream, dy, ids, nullptr, t, tt,
+                       word, pos, type, gamma, mean, rstd, b, t, h, nbw, p, seed, stream_id, dword, dpos, dtype, dgamma, dbeta);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -549,8 +573,8 @@ extern "C" int mc_add_ln_fwd(const mc_bf16* x, const mc_bf16* res, const float* 
                              float* mean, float* rstd, void* stream) {
     MC_CHECK(x && res && gamma && beta && y && mean && rstd, "add_ln_fwd: null arg");
     MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_fwd: bad shape");
-    hipLaunchKernelGGL(add_ln_fwd_k, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, res, gamma, beta, eps, rows,
-                       h, p, seed, stream_id, y, mean, rstd);
+    hipLaunchKernelGGL(add_ln_fwd_k<false>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, res, nullptr, gamma,
+                       beta, eps, rows, h, p, seed, stream_id, y, mean, rstd);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -562,8 +586,8 @@ extern "C" int mc_add_ln_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16*
     MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_bwd: bad shape");
     long long blocks = (rows + 3) / 4;
     if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(add_ln_bwd_k, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma, mean, rstd, rows,
-                       h, p, seed, stream_id, dx, dres, dgamma, dbeta);
+    hipLaunchKernelGGL(add_ln_bwd_k<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy, x, res, nullptr, gamma, mean,
+                       rstd, rows, h, p, seed, stream_id, dx, dres, dgamma, dbeta);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -638,6 +662,152 @@ extern "C" int mc_eos_gather(const mc_bf16* hid, const long long* mask, int b, i
 extern "C" int mc_eos_scatter(const float* dout, const long long* mask, int b, int t, int h, mc_bf16* dhid, void* stream) {
     MC_CHECK(dout && mask && dhid && b > 0 && t > 0 && h > 0, "eos_scatter: bad args");
     hipLaunchKernelGGL(eos_scatter_k, dim3(b), dim3(256), 0, (hipStream_t)stream, dout, mask, t, h, dhid);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ packed rows
+// The packed text encoder (BertModelHIP.set_packed) keeps only the real tokens of a [b, t] batch: sequence i owns rows
+// cu_seqlens[i] .. cu_seqlens[i+1]-1 of an [R, h] matrix, row_map[r] is the padded row i*t + position of packed row r
+// (-1 for the alignment rows behind the last sequence).  [ref: model/modules/text_encoder.py:47-49; model/clip.py:65-75]
+namespace {
+
+// out[i, :] = float(src[idx[i], :])
+__global__ void rows_gather_k(const bf16_t* __restrict__ src, const int* __restrict__ idx, int h, float* __restrict__ out) {
+    const long long r = idx[blockIdx.x];
+    for (int c = threadIdx.x; c < h; c += blockDim.x) out[(long long)blockIdx.x * h + c] = bf2f(src[r * h + c]);
+}
+// dsrc[idx[i], :] = dout[i, :]   (dsrc zero-filled by the caller; idx has no duplicates)
+__global__ void rows_scatter_k(const float* __restrict__ dout, const int* __restrict__ idx, int h, bf16_t* __restrict__ dsrc) {
+    const long long r = idx[blockIdx.x];
+    for (int c = threadIdx.x; c < h; c += blockDim.x) dsrc[r * h + c] = f2bf(dout[(long long)blockIdx.x * h + c]);
+}
+__global__ void segment_mean_fwd_k(const bf16_t* __restrict__ src, const int* __restrict__ cu, int h, float* __restrict__ out) {
+    const int r0 = cu[blockIdx.x], r1 = cu[blockIdx.x + 1];
+    const float n = fmaxf((float)(r1 - r0), 1e-9f);             // [ref: model/clip.py:73 torch.clamp(sum_mask, min=1e-9)]
+    for (int c = threadIdx.x; c < h; c += blockDim.x) {
+        float s = 0.f;
+        for (long long r = r0; r < r1; ++r) s += bf2f(src[r * h + c]);
+        out[(long long)blockIdx.x * h + c] = s / n;
+    }
+}
+// one workgroup per packed row: dsrc[r, :] = dout[seq(r), :] / len, zeros in the alignment rows
+__global__ void segment_mean_bwd_k(const float* __restrict__ dout, const int* __restrict__ cu, const int* __restrict__ row_map,
+                                   int t, int h, bf16_t* __restrict__ dsrc) {
+    const long long r = blockIdx.x;
+    const int pr = row_map[r];
+    const int i = pr < 0 ? 0 : pr / t;
+    const float n = fmaxf((float)(cu[i + 1] - cu[i]), 1e-9f);
+    for (int c = threadIdx.x; c < h; c += blockDim.x) dsrc[r * h + c] = pr < 0 ? (bf16_t)0 : f2bf(dout[(long long)i * h + c] / n);
+}
+// one workgroup per padded row: dst[i*t + pos, :] = pos < len_i ? src[cu[i] + pos, :] : 0     (16-byte chunks)
+__global__ void unpack_rows_k(const bf16_t* __restrict__ src, const int* __restrict__ cu, int t, int h, bf16_t* __restrict__ dst) {
+    const long long pr = blockIdx.x;
+    const int i = (int)(pr / t), pos = (int)(pr % t);
+    const bool real = pos < cu[i + 1] - cu[i];
+    const long long r = (long long)cu[i] + pos;
+    for (int v = threadIdx.x; v < h / 8; v += blockDim.x)
+        *reinterpret_cast<uint4*>(dst + pr * h + v * 8) = real ? *reinterpret_cast<const uint4*>(src + r * h + v * 8) : make_uint4(0u, 0u, 0u, 0u);
+}
+// one workgroup per packed row: dst[r, :] = row_map[r] >= 0 ? src[row_map[r], :] : 0
+__global__ void pack_rows_k(const bf16_t* __restrict__ src, const int* __restrict__ row_map, int h, bf16_t* __restrict__ dst) {
+    const long long r = blockIdx.x;
+    const long long pr = row_map[r];
+    for (int v = threadIdx.x; v < h / 8; v += blockDim.x)
+        *reinterpret_cast<uint4*>(dst + r * h + v * 8) = pr >= 0 ? *reinterpret_cast<const uint4*>(src + pr * h + v * 8) : make_uint4(0u, 0u, 0u, 0u);
+}
+
+}  // namespace
+
+extern "C" int mc_bert_embed_rows_fwd(const long long* ids, const long long* tt, const int* pos_ids, const int* row_map,
+                                      const float* word, const float* pos, const float* type, const float* gamma,
+                                      const float* beta, float eps, long long rows, int h, float p, unsigned long long seed,
+                                      unsigned int stream_id, mc_bf16* y, float* mean, float* rstd, void* stream) {
+    MC_CHECK(ids && pos_ids && row_map && word && pos && type && gamma && beta && y && mean && rstd, "embed_rows_fwd: null arg");
+    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "embed_rows_fwd: hidden must be a multiple of 8 and <= 1024");
+    hipLaunchKernelGGL(embed_fwd_k<true>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, ids, tt, pos_ids, row_map,
+                       word, pos, type, gamma, beta, eps, rows, 1, h, p, seed, stream_id, y, mean, rstd);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_bert_embed_rows_bwd(const mc_bf16* dy, const long long* ids, const long long* tt, const int* cu_seqlens,
+                                      const float* word, const float* pos, const float* type, const float* gamma,
+                                      const float* mean, const float* rstd, int b, int max_len, int t_pad, int h, float p,
+                                      unsigned long long seed, unsigned int stream_id, float* dword, float* dpos,
+                                      float* dtype, float* dgamma, float* dbeta, void* stream) {
+    MC_CHECK(dy && ids && cu_seqlens && word && pos && type && gamma && mean && rstd && dword && dpos && dtype && dgamma && dbeta,
+             "embed_rows_bwd: null arg");
+    MC_CHECK(b > 0 && max_len > 0 && t_pad >= max_len && h > 0 && h % 8 == 0 && h <= 1024, "embed_rows_bwd: bad shape");
+    int nbw = 2048 / max_len;
+    if (nbw < 1) nbw = 1;
+    if (nbw > b) nbw = b;
+    long long waves = (long long)max_len * nbw;
+    hipLaunchKernelGGL(embed_bwd_k<true>, dim3(mc_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream, dy, ids, cu_seqlens, t_pad,
+                       tt, word, pos, type, gamma, mean, rstd, b, max_len, h, nbw, p, seed, stream_id, dword, dpos, dtype,
+                       dgamma, dbeta);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_add_ln_rows_fwd(const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma,
+                                  const float* beta, float eps, long long rows, int h, float p, unsigned long long seed,
+                                  unsigned int stream_id, mc_bf16* y, float* mean, float* rstd, void* stream) {
+    MC_CHECK(x && res && row_map && gamma && beta && y && mean && rstd, "add_ln_rows_fwd: null arg");
+    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_rows_fwd: bad shape");
+    hipLaunchKernelGGL(add_ln_fwd_k<true>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, res, row_map, gamma,
+                       beta, eps, rows, h, p, seed, stream_id, y, mean, rstd);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_add_ln_rows_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map,
+                                  const float* gamma, const float* mean, const float* rstd, long long rows, int h, float p,
+                                  unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres,
+                                  float* dgamma, float* dbeta, void* stream) {
+    MC_CHECK(dy && x && res && row_map && gamma && mean && rstd && dx && dres && dgamma && dbeta, "add_ln_rows_bwd: null arg");
+    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_rows_bwd: bad shape");
+    long long blocks = (rows + 3) / 4;
+    if (blocks > 512) blocks = 512;
+    hipLaunchKernelGGL(add_ln_bwd_k<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy, x, res, row_map, gamma, mean,
+                       rstd, rows, h, p, seed, stream_id, dx, dres, dgamma, dbeta);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_rows_gather(const mc_bf16* src, const int* idx, int n, int h, float* out, void* stream) {
+    MC_CHECK(src && idx && out && n > 0 && h > 0, "rows_gather: bad args");
+    hipLaunchKernelGGL(rows_gather_k, dim3(n), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, idx, h, out);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_rows_scatter(const float* dout, const int* idx, int n, int h, mc_bf16* dsrc, void* stream) {
+    MC_CHECK(dout && idx && dsrc && n > 0 && h > 0, "rows_scatter: bad args");
+    hipLaunchKernelGGL(rows_scatter_k, dim3(n), dim3(256), 0, (hipStream_t)stream, dout, idx, h, (bf16_t*)dsrc);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_segment_mean_fwd(const mc_bf16* src, const int* cu_seqlens, int b, int h, float* out, void* stream) {
+    MC_CHECK(src && cu_seqlens && out && b > 0 && h > 0, "segment_mean_fwd: bad args");
+    hipLaunchKernelGGL(segment_mean_fwd_k, dim3(b), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, cu_seqlens, h, out);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_segment_mean_bwd(const float* dout, const int* cu_seqlens, const int* row_map, long long rows, int t, int h,
+                                   mc_bf16* dsrc, void* stream) {
+    MC_CHECK(dout && cu_seqlens && row_map && dsrc && rows > 0 && t > 0 && h > 0, "segment_mean_bwd: bad args");
+    hipLaunchKernelGGL(segment_mean_bwd_k, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, dout, cu_seqlens, row_map, t, h,
+                       (bf16_t*)dsrc);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_unpack_rows(const mc_bf16* src, const int* cu_seqlens, int b, int t, int h, mc_bf16* dst, void* stream) {
+    MC_CHECK(src && cu_seqlens && dst && b > 0 && t > 0 && h > 0 && h % 8 == 0, "unpack_rows: bad args (h % 8 == 0)");
+    hipLaunchKernelGGL(unpack_rows_k, dim3((unsigned)((long long)b * t)), dim3(128), 0, (hipStream_t)stream, (const bf16_t*)src,
+                       cu_seqlens, t, h, (bf16_t*)dst);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_pack_rows(const mc_bf16* src, const int* row_map, long long rows, int h, mc_bf16* dst, void* stream) {
+    MC_CHECK(src && row_map && dst && rows > 0 && h > 0 && h % 8 == 0, "pack_rows: bad args (h % 8 == 0)");
+    hipLaunchKernelGGL(pack_rows_k, dim3((unsigned)rows), dim3(128), 0, (hipStream_t)stream, (const bf16_t*)src, row_map, h,
+                       (bf16_t*)dst);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -179,6 +179,19 @@ _SIGS = {
     "mc_mask_bias": ([P, P, LL, P], I),
     "mc_eos_gather": ([P, P, I, I, I, P, P], I),
     "mc_eos_scatter": ([P, P, I, I, I, P, P], I),
+    "mc_attn_varlen_supported": ([I, I], I),
+    "mc_attn_varlen_fwd": ([P, P, P, I, I, I, LL, I, F, F, ULL, U, P, P, P], I),
+    "mc_attn_varlen_bwd": ([P, P, P, P, P, I, I, I, LL, I, F, F, ULL, U, P, P], I),
+    "mc_bert_embed_rows_fwd": ([P, P, P, P, P, P, P, P, P, F, LL, I, F, ULL, U, P, P, P, P], I),
+    "mc_bert_embed_rows_bwd": ([P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, ULL, U, P, P, P, P, P, P], I),
+    "mc_add_ln_rows_fwd": ([P, P, P, P, P, F, LL, I, F, ULL, U, P, P, P, P], I),
+    "mc_add_ln_rows_bwd": ([P, P, P, P, P, P, P, LL, I, F, ULL, U, P, P, P, P, P], I),
+    "mc_rows_gather": ([P, P, I, I, P, P], I),
+    "mc_rows_scatter": ([P, P, I, I, P, P], I),
+    "mc_segment_mean_fwd": ([P, P, I, I, P, P], I),
+    "mc_segment_mean_bwd": ([P, P, P, LL, I, I, P, P], I),
+    "mc_unpack_rows": ([P, P, I, I, I, P, P], I),
+    "mc_pack_rows": ([P, P, LL, I, P, P], I),
     "mc_sgemm": ([P, LL, LL, P, LL, LL, P, LL, I, I, I, F, F, P, P, P, P], I),
     "mc_sgemm_ws_floats": ([I, I, I], LL),
     "mc_scale_f32": ([P, P, F, P, LL, P], I),

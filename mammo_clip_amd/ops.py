@@ -1122,6 +1122,172 @@ def eos_scatter(dout, mask, b, t, h):
     return dh
 
 
+# ------------------------------------------------------------------------------------------- packed text rows
+class PackedRows:
+    """Host-built description of a packed batch (include/mammoclip_hip.h, "Packed text encoder"): ``rows`` packed rows (the
+    real tokens of ``b`` sequences plus alignment rows up to a multiple of ``ALIGN``) of a [b, t0] token batch.  ``t`` is the
+    T of the padded layout that the dropout indices refer to: t0 rounded up to 8, what BertModelHIP's padded path runs.
+    The int32 index arrays live on the device after ONE host-to-device copy (``to``)."""
+    ALIGN = 8       # GEMM operands and the 16-byte-row kernels want a multiple of 8 rows
+
+    def __init__(self, lengths, t0):
+        self.lengths = [int(n) for n in lengths]
+        self.b, self.t0, self.t = len(self.lengths), int(t0), -(-int(t0) // 8) * 8
+        if min(self.lengths) < 1 or max(self.lengths) > self.t0:
+            raise ValueError("PackedRows: every sequence needs 1 <= length <= t0")
+        self.max_len = max(self.lengths)
+        self.real = sum(self.lengths)
+        self.rows = -(-self.real // self.ALIGN) * self.ALIGN
+        self.host = pack_index_arrays(self.lengths, self.t0, self.t, self.rows)
+        self.cu = self.order = self.eos = self.row_map = self.pos = self.src = None
+
+    def to(self, device):
+        d = self.host.to(device, non_blocking=True)
+        b, r = self.b, self.rows
+        self.cu, self.order, self.eos = d[:b + 1], d[b + 1:2 * b + 1], d[2 * b + 1:3 * b + 1]
+        self.row_map, self.pos, self.src = d[3 * b + 1:3 * b + 1 + r], d[3 * b + 1 + r:3 * b + 1 + 2 * r], d[3 * b + 1 + 2 * r:]
+        return self
+
+
+def pack_index_arrays(lengths, t0, t, rows):
+    """int32 host tensor [cu_seqlens (b+1) | order (b) | eos rows (b) | row_map (rows) | pos_ids (rows) | src (rows)]:
+    order = sequence indices, longest first (stable); eos = cu[i+1]-1; row_map[r] = i*t + pos (-1 in alignment rows);
+    src[r] = i*t0 + pos, the element of the flattened [b, t0] token tensors (alignment rows: element 0, a valid index)."""
+    ln = torch.as_tensor(lengths, dtype=torch.int64)
+    b = ln.numel()
+    cu = torch.zeros(b + 1, dtype=torch.int64)
+    cu[1:] = torch.cumsum(ln, 0)
+    real = int(cu[-1])
+    seq = torch.repeat_interleave(torch.arange(b), ln)
+    pos = torch.arange(real) - cu[:-1][seq]
+    row_map = torch.full((rows,), -1, dtype=torch.int64)
+    row_map[:real] = seq * t + pos
+    pos_ids = torch.zeros(rows, dtype=torch.int64)
+    pos_ids[:real] = pos
+    src = torch.zeros(rows, dtype=torch.int64)
+    src[:real] = seq * t0 + pos
+    order = torch.sort(ln, descending=True, stable=True).indices
+    return torch.cat([cu, order, cu[1:] - 1, row_map, pos_ids, src]).to(torch.int32)
+
+
+def prefix_lengths(mask):
+    """int64 [b] on the mask's device: the length of every row of a [b, t] attention mask that is a contiguous non-empty
+    prefix 1..10..0 (what the tokenizer produces), 0 for any other row (holes, all zeros).  No synchronisation."""
+    m = mask != 0
+    ln = m.sum(1)
+    ok = (m == (torch.arange(m.shape[1], device=m.device)[None, :] < ln[:, None])).all(1)
+    return ln * ok
+
+
+def packable(lengths, t0):
+    """whether a call with these prefix_lengths (a list) takes the packed path: every mask a prefix, and at least one padded
+    token to skip (an all-ones batch runs the padded launches)"""
+    return min(lengths) >= 1 and min(lengths) < t0
+
+
+def attn_varlen_supported(max_len, head_dim):
+    return bool(L.load().mc_attn_varlen_supported(int(max_len), int(head_dim)))
+
+
+def attn_varlen_fwd(qkv, pk, nh, alpha, p, seed, sid):
+    """ctx [rows, nh*64] and lse [rows, nh, 2] from packed qkv [rows, 3*nh*64]; alignment rows of ctx are zeros"""
+    ctx = empty((pk.rows, nh * 64), BF16, qkv)
+    lse = empty((pk.rows, nh, 2), torch.float32, qkv)
+    L.call("mc_attn_varlen_fwd", _p(qkv), _p(pk.cu), _p(pk.order), pk.b, pk.max_len, pk.t, pk.rows, nh, float(alpha), float(p),
+           int(seed), int(sid), _p(ctx), _p(lse), _st())
+    return ctx, lse
+
+
+def attn_varlen_bwd(qkv, pk, dctx, lse, nh, alpha, p, seed, sid):
+    dqkv = empty(qkv.shape, BF16, qkv)
+    L.call("mc_attn_varlen_bwd", _p(qkv), _p(pk.cu), _p(pk.order), _p(dctx), _p(lse), pk.b, pk.max_len, pk.t, pk.rows, nh,
+           float(alpha), float(p), int(seed), int(sid), _p(dqkv), _st())
+    return dqkv
+
+
+def bert_embed_rows_fwd(ids, tt, pk, word, pos, typ, gamma, beta, eps, p, seed, sid):
+    h = word.shape[1]
+    y = empty((pk.rows, h), BF16, word)
+    mean = empty((pk.rows,), torch.float32, word)
+    rstd = empty((pk.rows,), torch.float32, word)
+    L.call("mc_bert_embed_rows_fwd", _p(ids), _p(tt), _p(pk.pos), _p(pk.row_map), _p(word), _p(pos), _p(typ), _p(gamma), _p(beta),
+           eps, pk.rows, h, float(p), int(seed), int(sid), _p(y), _p(mean), _p(rstd), _st())
+    return y, mean, rstd
+
+
+def bert_embed_rows_bwd(dy, ids, tt, pk, word, pos, typ, gamma, mean, rstd, p, seed, sid):
+    h = word.shape[1]
+    dword, dpos, dtyp = torch.zeros_like(word), torch.zeros_like(pos), torch.zeros_like(typ)
+    dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
+    L.call("mc_bert_embed_rows_bwd", _p(dy), _p(ids), _p(tt), _p(pk.cu), _p(word), _p(pos), _p(typ), _p(gamma), _p(mean),
+           _p(rstd), pk.b, pk.max_len, pk.t, h, float(p), int(seed), int(sid), _p(dword), _p(dpos), _p(dtyp), _p(dgamma),
+           _p(dbeta), _st())
+    return dword, dpos, dtyp, dgamma, dbeta
+
+
+def add_ln_rows_fwd(x, res, row_map, gamma, beta, eps, p, seed, sid):
+    rows, h = x.shape
+    y = empty((rows, h), BF16, x)
+    mean = empty((rows,), torch.float32, x)
+    rstd = empty((rows,), torch.float32, x)
+    L.call("mc_add_ln_rows_fwd", _p(x), _p(res), _p(row_map), _p(gamma), _p(beta), eps, rows, h, float(p), int(seed), int(sid),
+           _p(y), _p(mean), _p(rstd), _st())
+    return y, mean, rstd
+
+
+def add_ln_rows_bwd(dy, x, res, row_map, gamma, mean, rstd, p, seed, sid):
+    rows, h = x.shape
+    dx, dres = empty((rows, h), BF16, x), empty((rows, h), BF16, x)
+    gb = torch.zeros((2,) + tuple(gamma.shape), dtype=gamma.dtype, device=gamma.device)
+    dgamma, dbeta = gb[0], gb[1]
+    L.call("mc_add_ln_rows_bwd", _p(dy), _p(x), _p(res), _p(row_map), _p(gamma), _p(mean), _p(rstd), rows, h, float(p),
+           int(seed), int(sid), _p(dx), _p(dres), _p(dgamma), _p(dbeta), _st())
+    return dx, dres, dgamma, dbeta
+
+
+def rows_gather(src, idx):
+    n, h = idx.numel(), src.shape[1]
+    out = empty((n, h), torch.float32, src)
+    L.call("mc_rows_gather", _p(src), _p(idx), n, h, _p(out), _st())
+    return out
+
+
+def rows_scatter(dout, idx, rows):
+    n, h = dout.shape
+    dsrc = torch.zeros((rows, h), dtype=BF16, device=dout.device)
+    L.call("mc_rows_scatter", _p(dout), _p(idx), n, h, _p(dsrc), _st())
+    return dsrc
+
+
+def segment_mean_fwd(src, pk):
+    h = src.shape[1]
+    out = empty((pk.b, h), torch.float32, src)
+    L.call("mc_segment_mean_fwd", _p(src), _p(pk.cu), pk.b, h, _p(out), _st())
+    return out
+
+
+def segment_mean_bwd(dout, pk):
+    h = dout.shape[1]
+    dsrc = empty((pk.rows, h), BF16, dout)
+    L.call("mc_segment_mean_bwd", _p(dout), _p(pk.cu), _p(pk.row_map), pk.rows, pk.t, h, _p(dsrc), _st())
+    return dsrc
+
+
+def unpack_rows(src, pk, t):
+    """[b*t, h] with the packed rows at their padded places and zeros elsewhere"""
+    h = src.shape[1]
+    dst = empty((pk.b * t, h), BF16, src)
+    L.call("mc_unpack_rows", _p(src), _p(pk.cu), pk.b, int(t), h, _p(dst), _st())
+    return dst
+
+
+def pack_rows(src, row_map):
+    rows, h = row_map.numel(), src.shape[1]
+    dst = empty((rows, h), BF16, src)
+    L.call("mc_pack_rows", _p(src), _p(row_map), rows, h, _p(dst), _st())
+    return dst
+
+
 # ------------------------------------------------------------------------------------------- heads / loss
 def sgemm(a, ars, acs, b, brs, bcs, c, ldc, m, n, k, alpha=1.0, beta=0.0, bias=None, alpha_dev=None):
     nws = L.load().mc_sgemm_ws_floats(m, n, k)
