@@ -96,7 +96,8 @@ constexpr int NDESC = 128;
 //   dA0[q] = sum_t dd[q + t - (K-1-pad)] wflip[t]        dW[K*K-1-t] += dd[q + t - (K-1-pad)] a0[q]
 // pair every staged dd value with the SAME (output pixel q, tap t), so the weight gradient is one more packed FMA beside each
 // FMA of the data gradient.  a0[q] is evaluated once, when output row q.y meets its first dd row (an A-deep register window of
-// a0 and of the packed e values, which the epilogue needs again when the row completes); the e rows therefore enter K-1 rows
+// a0, of silu'(bn0(e)) -- taken from the same sigmoid, so the epilogue evaluates none when the row completes -- and of the packed
+// e values, which the reductions need again); the e rows therefore enter K-1 rows
 // EARLIER than in MODE 1 and get an LDS tile of their own.  dd and e are read once, dZ0 is written once: 3 passes over the
 // expanded tensor instead of 5 (MODE 1: dd + e read, dZ0 written; MODE 2: dd + e read).
 // MODE 4 (round 6, mc_mbconv_xdw_fwd): the forward launch with the EXPAND 1x1 CONV of the MBConv block inside the staging
@@ -568,11 +569,12 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
 #pragma unroll
     for (int t = 0; t < ((BWW || FUSED) ? K * K : 1); ++t) dwa[t] = f32x2_t{0.f, 0.f};
     f32x2_t a0w[FUSED ? NCOL : 1][FUSED ? C::A : 1];       // FUSED: a0 = silu(bn0(e)) of the output rows in flight (0 where no pixel exists)
-    uint32_t ew[FUSED ? NCOL : 1][FUSED ? C::A : 1];       // ... and their packed e values (the epilogue needs them when the row completes)
+    uint32_t ew[FUSED ? NCOL : 1][FUSED ? C::A : 1];       // ... their packed e values (the reductions need e - mean when the row completes)
+    f32x2_t gw[FUSED ? NCOL : 1][FUSED ? C::A : 1];        // ... and silu'(bn0(e)), from the SAME sigmoid as a0: one exp + one rcp per element
 #pragma unroll
     for (int i = 0; i < (FUSED ? NCOL : 1); ++i)
 #pragma unroll
-        for (int a = 0; a < (FUSED ? C::A : 1); ++a) { a0w[i][a] = f32x2_t{0.f, 0.f}; ew[i][a] = 0u; }
+        for (int a = 0; a < (FUSED ? C::A : 1); ++a) { a0w[i][a] = f32x2_t{0.f, 0.f}; ew[i][a] = 0u; gw[i][a] = f32x2_t{0.f, 0.f}; }
     f32x2_t ssum = {0.f, 0.f}, ssq = {0.f, 0.f};
 
     // interval q: store block q (loaded in interval q-1), flush block q-2, load block q+1, compute block q-1.
@@ -580,9 +582,17 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
     stage_load(0, nbtot > 0);
     int q = 0;
     while (true) {
+        // descriptor refill: ONE call site per trip instead of one per unrolled phase (its integer divisions were inlined U times
+        // into the hot body for code that runs once per 64 blocks on one wave).  The refill that falls due at interval
+        // qr = 2 (mod 64), qr >= 66, runs at the start of the next trip, i.e. 1 .. U intervals late: it rewrites the slots of blocks
+        // qr-66 .. qr-3, which nobody reads any more (interval q touches blocks q-2 .. q+1), with blocks qr+62 .. qr+125, and the
+        // ring already holds every block up to qr+61.
+        if (wv == 0) {
+            const int qr = ((q - 3) & ~63) + 2;            // the latest due interval before this trip
+            if (qr >= 66 && qr >= q - C::U) gen_desc(qr + 62);
+        }
 #pragma unroll
         for (int ph = 0; ph < C::U; ++ph) {
-            if (wv == 0 && q >= 66 && ((q - 2) & 63) == 0) gen_desc(q + 62);   // refill the slots of blocks q-66 .. q-3
             const bool v_st = q < nbtot, v_ld = q + 1 < nbtot, v_cp = q >= 1 && q <= nbtot, v_fl = q >= 2 && !BWW;
             // (1) registers -> LDS for block q; finished rows of block q-2 -> global (EPI: then the e rows of block q)
             __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): the prefetched registers (see conv.hip)
@@ -640,7 +650,7 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
 #pragma unroll
                     for (int i = 0; i < NCOL; ++i)
 #pragma unroll
-                        for (int a = 0; a < C::A; ++a) { a0w[i][a] = f32x2_t{0.f, 0.f}; ew[i][a] = 0u; }
+                        for (int a = 0; a < C::A; ++a) { a0w[i][a] = f32x2_t{0.f, 0.f}; ew[i][a] = 0u; gw[i][a] = f32x2_t{0.f, 0.f}; }
                 }
                 const uint32_t* lin = s_in + ((q - 1) & 1) * C::IN_DW + ((x / C::LPI) * C::SEGP + x % C::LPI) * C::PXD + wv;
                 const uint32_t* le = s_e + ((q - 1) & 1) * C::OUT_DW + x * C::PXD + wv;
@@ -659,20 +669,23 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
                     }
                     {   // the output row whose FIRST dd row this is enters the window: e-tile row j, slot jr % A
                         const int s0 = jr % C::A;
-                        const bool e_ok = j < erhi;                    // (wave-uniform; rows beyond the item: a0 = 0)
+                        // (wave-uniform, folded into the column mask -- no branch in the block body; rows beyond the item: e = 0, a0 = 0.
+                        // The tile slot is read whatever it holds and masked BEFORE any arithmetic: no NaN pattern gets further)
+                        const uint32_t em = j < erhi ? 0xffffffffu : 0u;
 #pragma unroll
                         for (int i = 0; i < NCOL; ++i) {
-                            uint32_t ev = 0u;
-                            f32x2_t a = {0.f, 0.f};
-                            if (e_ok) {
-                                ev = le[(j * C::TOWP + i * 64) * C::PXD] & cm[i];
-                                const f32x2_t e2 = {bf_lo(ev), bf_hi(ev)};
-                                const f32x2_t sa = silu2_f(__builtin_elementwise_fma(e2, e_sc, e_sh));
-                                // pixels that do not exist (columns beyond the map / the strip): a0 = 0, whatever silu(shift) is
-                                a = f32x2_t{__uint_as_float(__float_as_uint(sa.x) & cm[i]), __uint_as_float(__float_as_uint(sa.y) & cm[i])};
-                            }
+                            const uint32_t m = cm[i] & em;
+                            const uint32_t ev = le[(j * C::TOWP + i * 64) * C::PXD] & m;
+                            const f32x2_t e2 = {bf_lo(ev), bf_hi(ev)};
+                            // ONE sigmoid per element gives a0 = z * s (silu2_f) and silu' = s * (1 + z * (1 - s)) (silu_grad2_f): the
+                            // same expressions, so a0 and dZ0 keep their bits
+                            const f32x2_t z = __builtin_elementwise_fma(e2, e_sc, e_sh);
+                            const f32x2_t sg = sigmoid2_f(z);
+                            const f32x2_t sa = z * sg;
                             ew[i][s0] = ev;
-                            a0w[i][s0] = a;
+                            // pixels that do not exist (columns beyond the map / the strip, rows beyond the item): a0 = 0, whatever silu(shift) is
+                            a0w[i][s0] = f32x2_t{__uint_as_float(__float_as_uint(sa.x) & m), __uint_as_float(__float_as_uint(sa.y) & m)};
+                            gw[i][s0] = sg * __builtin_elementwise_fma(z, f32x2_t{1.f, 1.f} - sg, f32x2_t{1.f, 1.f});
                         }
                     }
 #pragma unroll
@@ -689,22 +702,21 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
                     }
                     {   // output row complete: out-tile row j
                         const int sl = pmod_c(jr - (K - 1), C::A);
-                        const bool o_ok = j >= orlo && j < orhi;      // (wave-uniform)
+                        // (wave-uniform, folded into the column mask: rows that do not count add exact zeros -- r = 0 and e2 is the
+                        // masked e of the window, so no 0 * NaN)
+                        const uint32_t om = (j >= orlo && j < orhi) ? 0xffffffffu : 0u;
 #pragma unroll
                         for (int i = 0; i < NCOL; ++i) {
                             uint32_t* slot = lout + (j * C::TOWP + i * 64) * C::PXD;
                             const uint32_t ewv = ew[i][sl];
                             const f32x2_t e2 = {bf_lo(ewv), bf_hi(ewv)};
-                            const f32x2_t z = __builtin_elementwise_fma(e2, e_sc, e_sh);
-                            const f32x2_t dz = acc[i][sl] * silu_grad2_f(z);
+                            const f32x2_t dz = acc[i][sl] * gw[i][sl];
                             const uint32_t o2 = pack_bf2(dz.x, dz.y);
                             *slot = o2;
-                            if (o_ok) {
-                                const uint32_t m = o2 & cm[i];
-                                const f32x2_t r = {bf_lo(m), bf_hi(m)};          // reductions of the stored (rounded) dZ0
-                                ssum += r;
-                                ssq = __builtin_elementwise_fma(r, e2 - e_mu, ssq);
-                            }
+                            const uint32_t m = o2 & (cm[i] & om);
+                            const f32x2_t r = {bf_lo(m), bf_hi(m)};              // reductions of the stored (rounded) dZ0
+                            ssum += r;
+                            ssq = __builtin_elementwise_fma(r, e2 - e_mu, ssq);
                         }
                     }
                 }
@@ -741,34 +753,34 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
                     }
                     if (pmod_c(jr - (K - 1), S) == 0) {                 // an output row is complete: out-tile row j / S
                         const int sl = pmod_c(fdiv_c(jr - (K - 1), S), C::A);
-                        const bool o_ok = j / S >= orlo && j / S < orhi;  // (wave-uniform)
+                        // (wave-uniform, folded into the column mask: the block body has no branch, and rows that do not count add
+                        // exact zeros to the statistics)
+                        const uint32_t om = (j / S >= orlo && j / S < orhi) ? 0xffffffffu : 0u;
 #pragma unroll
                         for (int i = 0; i < NCOL; ++i) {
                             uint32_t* slot = lout + ((j / S) * C::TOWP + i * 64) * C::PXD;
+                            const uint32_t cmo = cm[i] & om;
                             if constexpr (EPI) {
                                 // (masked: the slots of columns that do not exist are never staged -- they hold what this lane
-                                // wrote there a block ago, and 0 * NaN must not reach the reductions)
-                                const uint32_t ew = *slot & cm[i];
+                                // wrote there a block ago, and 0 * NaN must not reach the reductions; rows that do not count are
+                                // masked the same way, so BOTH factors of the ssq update are zero for them)
+                                const uint32_t ew = *slot & cmo;
                                 const f32x2_t e2 = {bf_lo(ew), bf_hi(ew)};
                                 const f32x2_t z = __builtin_elementwise_fma(e2, e_sc, e_sh);
                                 const f32x2_t dz = acc[i][sl] * silu_grad2_f(z);
                                 const uint32_t o2 = pack_bf2(dz.x, dz.y);
                                 *slot = o2;
-                                if (o_ok) {
-                                    const uint32_t m = o2 & cm[i];
-                                    const f32x2_t r = {bf_lo(m), bf_hi(m)};          // reductions of the stored (rounded) dZ0
-                                    ssum += r;
-                                    ssq = __builtin_elementwise_fma(r, e2 - e_mu, ssq);   // centred: no cancelling difference at the end
-                                }
+                                const uint32_t m = o2 & cmo;
+                                const f32x2_t r = {bf_lo(m), bf_hi(m)};              // reductions of the stored (rounded) dZ0
+                                ssum += r;
+                                ssq = __builtin_elementwise_fma(r, e2 - e_mu, ssq);       // centred: no cancelling difference at the end
                             } else {
                                 const uint32_t o2 = pack_bf2(acc[i][sl].x, acc[i][sl].y);
                                 *slot = o2;
-                                if (o_ok) {
-                                    const uint32_t m = o2 & cm[i];
-                                    const f32x2_t r = {bf_lo(m), bf_hi(m)};          // statistics of the stored (rounded) tensor
-                                    ssum += r;
-                                    ssq = __builtin_elementwise_fma(r, r, ssq);
-                                }
+                                const uint32_t m = o2 & cmo;
+                                const f32x2_t r = {bf_lo(m), bf_hi(m)};              // statistics of the stored (rounded) tensor
+                                ssum += r;
+                                ssq = __builtin_elementwise_fma(r, r, ssq);
                             }
                         }
                     }
