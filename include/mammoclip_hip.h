@@ -554,6 +554,30 @@ int mc_ce_fwd_bwd(float* logits, int rows, int n, const long long* labels, int l
                   float* loss_out, float* row_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * evaluation metrics (retrieval.hip), fp32 in both storage builds.  a[N,D] image embeddings, b[M,D] text embeddings, both
+ * row-major; similarities <a_i, b_j> are exact-f32 products (f32-input MFMA, k ascending) and the N x M matrix is never
+ * written to memory: a workgroup owns 64 rows of a and a chunk of b and keeps only counts / short lists. */
+/* rank[i] = 1 + #{ j : <a_i,b_j> > <a_i,b_label[i]> }: the rank of the paired report, ties not counted (the paired
+ * similarity comes out of the same arithmetic, so a text never outranks itself); label[i] outside [0, M) gives rank[i] = -1
+ * [ref: evaluator.py:226-240 (cosine_similarity + one argsort per image)] */
+int mc_sim_rank(const float* a, const float* b, const int* label, int* rank, int N, int M, int D, void* stream);
+/* per row the k largest similarities and their text indices, score descending then index ascending; 1 <= k <= 32, k <= M.
+ * ws: mc_sim_topk_ws_bytes(N, M, k) bytes (O(N * k * splits)); the result does not depend on the split of M
+ * [ref: evaluator.py:226-232 (the head of the per-image argsort)] */
+long long mc_sim_topk_ws_bytes(int N, int M, int k);
+int mc_sim_topk(const float* a, const float* b, float* vals, int* idx, int N, int M, int D, int k, void* ws, void* stream);
+/* number of chunks M is split into by mc_sim_rank / mc_sim_topk: 0 = chosen per call (enough workgroups to fill the device
+ * when N is small), 1..64 = fixed (capped at the number of 128-text tiles).  Process-wide developer / test switch. */
+int mc_sim_set_splits(int splits);
+/* p[i,:] = softmax_j <a_i, b_j> over the M prompts, any M >= 1 [ref: evaluator.py:173] */
+int mc_sim_softmax(const float* a, const float* b, float* p, int N, int M, int D, void* stream);
+/* counts[0] = #{(p,n): score_p > score_n}, counts[1] = #{score_p == score_n} over all (positive, negative) pairs,
+ * counts[2] = positives (label != 0), counts[3] = negatives (label == 0); 64-bit integer atomics.  The host finishes
+ * AUROC = (counts[0] + 0.5 counts[1]) / (counts[2] counts[3]), the Mann-Whitney form of roc_curve + auc
+ * [ref: evaluator.py:176-177,180-181,188-189] */
+int mc_auroc_counts(const float* score, const int* label, long long* counts, int N, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * optimizer step of the hot loop [ref: breastclip/optimizer/__init__.py:28-29 ->
  * torch.optim.AdamW(model.parameters(), lr, weight_decay); trainer_ddp.py:300-303].  Multi-tensor, in place, fp32:
  *   p -= lr*wd*p;  m += (1-b1)(g-m);  v = b2*v + (1-b2) g*g;  p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)

@@ -198,6 +198,12 @@ _SIGS = {
     "mc_l2norm_fwd": ([P, I, I, P, P, P], I),
     "mc_l2norm_bwd": ([P, P, P, I, I, P, P], I),
     "mc_ce_fwd_bwd": ([P, I, I, P, I, F, F, P, P, P], I),
+    "mc_sim_rank": ([P, P, P, P, I, I, I, P], I),
+    "mc_sim_topk_ws_bytes": ([I, I, I], LL),
+    "mc_sim_topk": ([P, P, P, P, I, I, I, I, P, P], I),
+    "mc_sim_set_splits": ([I], I),
+    "mc_sim_softmax": ([P, P, P, I, I, I, P], I),
+    "mc_auroc_counts": ([P, P, P, I, P], I),
 }
 
 EXPORTS = sorted(list(_SIGS.keys()) + ["mc_last_error"])

@@ -1324,6 +1324,69 @@ def ce_fwd_bwd(logits, label_offset, w, loss_out, smoothing=0.0, labels=None):
            _p(row_ws), _st())
 
 
+# ------------------------------------------------------------------------------------------- evaluation metrics
+def _f32_rows(*ts):
+    _chk_dev(*ts)
+    for t in ts:
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise L.MammoClipHipError("the similarity kernels take contiguous fp32 [rows, D] tensors")
+    if len({t.shape[1] for t in ts}) != 1 or len({t.device for t in ts}) != 1:
+        raise L.MammoClipHipError("the similarity kernels need one embedding width and one device")
+
+
+def sim_rank(a, b, label):
+    """rank [N] int32 of text ``label[i]`` among the M texts for image i: 1 + the number of strictly larger similarities; -1
+    where the label is outside [0, M).  The N x M similarities are never stored."""
+    _f32_rows(a, b)
+    n, d = a.shape
+    label = label.to(device=a.device, dtype=torch.int32).contiguous()
+    if label.shape != (n,):
+        raise L.MammoClipHipError("sim_rank: one label per image")
+    rank = empty((n,), torch.int32, a)
+    _note(4 * (a.numel() + b.numel()), 2 * n * b.shape[0] * d)
+    L.call("mc_sim_rank", _p(a), _p(b), _p(label), _p(rank), n, b.shape[0], d, _st())
+    return rank
+
+
+def sim_topk(a, b, k):
+    """(values [N, k] fp32, indices [N, k] int32): the k most similar texts per image, score descending then index ascending"""
+    _f32_rows(a, b)
+    n, d = a.shape
+    m, k = b.shape[0], int(k)
+    vals, idx = empty((n, max(k, 1)), torch.float32, a), empty((n, max(k, 1)), torch.int32, a)   # (a bad k fails in the call)
+    ws = empty((max(1, L.load().mc_sim_topk_ws_bytes(n, m, k)),), torch.uint8, a)
+    _note(4 * (a.numel() + b.numel()), 2 * n * m * d)
+    L.call("mc_sim_topk", _p(a), _p(b), _p(vals), _p(idx), n, m, d, k, _p(ws), _st())
+    return vals, idx
+
+
+def sim_set_splits(splits):
+    """number of chunks the texts are split into by sim_rank / sim_topk (0: chosen per call); results do not depend on it"""
+    L.call("mc_sim_set_splits", int(splits))
+
+
+def sim_softmax(a, b):
+    """softmax over the M rows of b of the similarities a @ b.T: [N, M] fp32"""
+    _f32_rows(a, b)
+    n, d = a.shape
+    p = empty((n, b.shape[0]), torch.float32, a)
+    L.call("mc_sim_softmax", _p(a), _p(b), _p(p), n, b.shape[0], d, _st())
+    return p
+
+
+def auroc_counts(score, label):
+    """int64 [4] on the device: pairs (positive, negative) with s_pos > s_neg, with s_pos == s_neg, positives, negatives"""
+    _chk_dev(score, label)
+    if score.dtype != torch.float32 or score.dim() != 1 or not score.is_contiguous():
+        raise L.MammoClipHipError("auroc_counts: contiguous fp32 [N] scores")
+    label = label.to(device=score.device, dtype=torch.int32).contiguous()
+    if label.shape != score.shape:
+        raise L.MammoClipHipError("auroc_counts: one label per score")
+    counts = empty((4,), torch.int64, score)
+    L.call("mc_auroc_counts", _p(score), _p(label), _p(counts), score.numel(), _st())
+    return counts
+
+
 # ------------------------------------------------------------------------------------------- dispatcher-visible operators
 # The 1x1-convolution / linear and depthwise-convolution calls of the model go through ``torch.ops.mammoclip.*`` (registered
 # in custom_ops.py with torch.library: schema + HIP implementation + meta implementation; ~2.5 us of dispatcher per call):
