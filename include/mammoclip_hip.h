@@ -578,6 +578,23 @@ int mc_sim_softmax(const float* a, const float* b, float* p, int N, int M, int D
 int mc_auroc_counts(const float* score, const int* label, long long* counts, int N, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * training augmentation (augment.hip): flips, affine and elastic warp of the reference's train transform as one gather per
+ * output pixel, all integer; the specification is the docstring of mammo_clip_amd/augment.py and the
+ * result equals its numpy path byte for byte [ref: data/data_utils.py:25-62; data/datasets/imagetext.py:126-160].
+ * src: one uint8 plane per source image, element (i, y, x) at src[i*sn + y*sh + x*sw] (any strides, e.g. a channel of an HWC
+ * array); params: device int32 [n_out][16] rows (source index, flags, Q16 inverse affine, alpha_q8, seed; a row whose source
+ * index is outside [0, n_src) reads nothing and writes zeros); taps: device int32 [2*radius + 1], sum 32768;
+ * dst: dense uint8 [n_out][3][h][w].  1 <= h, w <= 16384; 1 <= radius <= min(128, min(h, w) - 1).
+ * ws: ws_bytes >= mc_augment_ws_bytes(1, h, w) bytes; the images are worked through in chunks of as many as fit, and the
+ * result does not depend on the chunking.  mc_augment_ws_bytes returns 0 for extents outside the range. */
+long long mc_augment_ws_bytes(int n_out, int h, int w);
+int mc_augment_u8(const unsigned char* src, long long sn, long long sh, long long sw, int n_src, const int* params, int n_out,
+                  const int* taps, int radius, int h, int w, unsigned char* dst, void* ws, long long ws_bytes, void* stream);
+/* which of the two kernels mc_augment_u8 launches: bit 0 the noise + horizontal pass, bit 1 the vertical pass + warp; 3 (the
+ * default) is the op, 1 and 2 exist to time each kernel on its own (scripts/augment_bench.py).  Process-wide developer switch. */
+int mc_augment_set_stages(int mask);
+
+/* ------------------------------------------------------------------------------------------------
  * optimizer step of the hot loop [ref: breastclip/optimizer/__init__.py:28-29 ->
  * torch.optim.AdamW(model.parameters(), lr, weight_decay); trainer_ddp.py:300-303].  Multi-tensor, in place, fp32:
  *   p -= lr*wd*p;  m += (1-b1)(g-m);  v = b2*v + (1-b2) g*g;  p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)

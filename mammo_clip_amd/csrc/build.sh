@@ -9,7 +9,7 @@
 set -e
 cd "$(dirname "$0")"
 if [ "${MC_REBUILD:-0}" = "1" ]; then rm -f ../lib/*.o ../lib/f16/*.o ../lib/libmammoclip_hip.so ../lib/libmammoclip_hip_f16.so; fi
-SRCS="gemm gemm256 gemm256_tn fp8 gemm_rows gemm_wgrad_rows conv conv_lane bnact bnfold bert attn attn_varlen head retrieval optim util"
+SRCS="gemm gemm256 gemm256_tn fp8 gemm_rows gemm_wgrad_rows conv conv_lane bnact bnfold bert attn attn_varlen head retrieval augment optim util"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result"
 pids=()
 compile_variant() {   # $1 = object directory, $2 = extra flags

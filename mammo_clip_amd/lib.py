@@ -204,6 +204,9 @@ _SIGS = {
     "mc_sim_set_splits": ([I], I),
     "mc_sim_softmax": ([P, P, P, I, I, I, P], I),
     "mc_auroc_counts": ([P, P, P, I, P], I),
+    "mc_augment_ws_bytes": ([I, I, I], LL),
+    "mc_augment_u8": ([P, LL, LL, LL, I, P, I, P, I, I, I, P, P, LL, P], I),
+    "mc_augment_set_stages": ([I], I),
 }
 
 EXPORTS = sorted(list(_SIGS.keys()) + ["mc_last_error"])

@@ -1387,6 +1387,40 @@ def auroc_counts(score, label):
     return counts
 
 
+# ------------------------------------------------------------------------------------------- training augmentation
+def augment_u8(src, params, sigma, out=None, ws_bytes=None):
+    """uint8 [n, 3, H, W]: flips / affine / elastic warp of the planes ``src`` (uint8 [n_src, H, W], any strides) under the
+    int32 [n, 16] rows ``params`` (numpy or tensor), the specification of mammo_clip_amd/augment.py.  ``ws_bytes``: size of the
+    workspace (default: all images in one chunk; at least one image's need); the result does not depend on it."""
+    import numpy as np
+    from . import augment as A
+    _chk_dev(src)
+    if src.dtype != torch.uint8 or src.dim() != 3:
+        raise L.MammoClipHipError("augment_u8: src must be uint8 [n_src, H, W]")
+    n_src, h, w = src.shape
+    rows = params.cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
+    rows = A._check_params(rows, n_src)                         # a source index out of range is rejected here, not read
+    taps = A.gaussian_taps(sigma, h, w)                         # raises for sigma < 0.5 and a radius the extents cannot take
+    n = rows.shape[0]
+    lib = L.load()
+    need, one = lib.mc_augment_ws_bytes(n, h, w), lib.mc_augment_ws_bytes(1, h, w)
+    if one <= 0:
+        raise L.MammoClipHipError(f"augment_u8: extents {h} x {w} outside [1, {A.MAX_EXTENT}]")
+    ws = empty((need if ws_bytes is None else int(ws_bytes),), torch.uint8, src)
+    if out is None:
+        out = empty((n, 3, h, w), torch.uint8, src)
+    elif out.shape != (n, 3, h, w) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != src.device:
+        raise L.MammoClipHipError("augment_u8: out must be a contiguous uint8 [n, 3, H, W] tensor on the source's device")
+    # one pageable upload of the few integers of the call: rows and taps together
+    host = torch.from_numpy(np.concatenate([np.ascontiguousarray(rows).reshape(-1), taps]).astype(np.int32))
+    dev = host.to(src.device)
+    sn, sh, sw = src.stride()
+    _note(n * h * w * 7)                                        # four source taps + three planes per output pixel
+    L.call("mc_augment_u8", _p(src), sn, sh, sw, n_src, _p(dev), n, dev.data_ptr() + rows.size * 4, (taps.size - 1) // 2, h, w,
+           _p(out), _p(ws), ws.numel(), _st())
+    return out
+
+
 # ------------------------------------------------------------------------------------------- dispatcher-visible operators
 # The 1x1-convolution / linear and depthwise-convolution calls of the model go through ``torch.ops.mammoclip.*`` (registered
 # in custom_ops.py with torch.library: schema + HIP implementation + meta implementation; ~2.5 us of dispatcher per call):
