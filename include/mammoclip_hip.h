@@ -485,7 +485,7 @@ int mc_eos_scatter(const float* dout, const long long* mask, int b, int t, int h
  * model/modules/text_encoder.py:47-49]; the padded rows are never read by a real token, so leaving them out changes
  * no result.  Every dropout mask below is the one the padded entry point draws for the same (seed, stream_id):
  * the element index is formed from the padded row. */
-/* Fused self-attention on packed rows (attn_varlen.hip), head size 64, 1 <= len_i <= max_len <= 256:
+/* Fused self-attention on packed rows (attn.hip, packed view), head size 64, 1 <= len_i <= max_len <= 256:
  *   ctx[rows, nh*64] = dropout(softmax(alpha * Q K^T)) V   per (sequence, head) over the sequence's own tokens
  * -- mc_attn_fwd on the padded batch with a 1..10..0 mask, without the padded rows
  * [ref: model/modules/text_encoder.py:47-49 -> transformers BertSelfAttention.forward].  qkv = [rows, 3*nh*64];

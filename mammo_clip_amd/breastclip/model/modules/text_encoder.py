@@ -32,30 +32,11 @@ class BertConfigLite:
 
 
 class _EmbedFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, word, pos, typ, gamma, beta, ids, tt, eps, p, seed, sid):
-        y, mean, rstd = ops.bert_embed_fwd(ids, tt, word, pos, typ, gamma, beta, eps, p, seed, sid)
-        ctx.cfg = (p, seed, sid)
-        ctx.params = (word, pos, typ, gamma, beta)
-        ctx.save_for_backward(word, pos, typ, gamma, ids, tt, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        word, pos, typ, gamma, ids, tt, mean, rstd = ctx.saved_tensors
-        p, seed, sid = ctx.cfg
-        dword, dpos, dtyp, dgamma, dbeta = ops.bert_embed_bwd(dy.contiguous(), ids, tt, word, pos, typ, gamma, mean, rstd,
-                                                              p, seed, sid)
-        dword[0].zero_()       # nn.Embedding(padding_idx=0) never accumulates a gradient for the [PAD] row
-        return ops.deliver_param_grads(ctx.params, (dword, dpos, dtyp, dgamma, dbeta)) + (None,) * 6
-
-
-class _EmbedPackedFn(torch.autograd.Function):
-    """_EmbedFn on packed rows: ``ids`` / ``tt`` hold the real tokens in packed order (ops.PackedRows)."""
+    """``pk`` (ops.PackedRows) set: ``ids`` / ``tt`` hold the real tokens in packed order."""
 
     @staticmethod
     def forward(ctx, word, pos, typ, gamma, beta, ids, tt, pk, eps, p, seed, sid):
-        y, mean, rstd = ops.bert_embed_rows_fwd(ids, tt, pk, word, pos, typ, gamma, beta, eps, p, seed, sid)
+        y, mean, rstd = ops.bert_embed_fwd(ids, tt, word, pos, typ, gamma, beta, eps, p, seed, sid, pk=pk)
         ctx.cfg = (pk, p, seed, sid)
         ctx.params = (word, pos, typ, gamma, beta)
         ctx.save_for_backward(word, pos, typ, gamma, ids, tt, mean, rstd)
@@ -65,9 +46,9 @@ class _EmbedPackedFn(torch.autograd.Function):
     def backward(ctx, dy):
         word, pos, typ, gamma, ids, tt, mean, rstd = ctx.saved_tensors
         pk, p, seed, sid = ctx.cfg
-        dword, dpos, dtyp, dgamma, dbeta = ops.bert_embed_rows_bwd(dy.contiguous(), ids, tt, pk, word, pos, typ, gamma, mean,
-                                                                   rstd, p, seed, sid)
-        dword[0].zero_()       # nn.Embedding(padding_idx=0), as in _EmbedFn
+        dword, dpos, dtyp, dgamma, dbeta = ops.bert_embed_bwd(dy.contiguous(), ids, tt, word, pos, typ, gamma, mean, rstd,
+                                                              p, seed, sid, pk=pk)
+        dword[0].zero_()       # nn.Embedding(padding_idx=0) never accumulates a gradient for the [PAD] row
         return ops.deliver_param_grads(ctx.params, (dword, dpos, dtyp, dgamma, dbeta)) + (None,) * 7
 
 
@@ -147,19 +128,15 @@ class _LayerFn(torch.autograd.Function):
                      sA=(nh * t * t, t * t), sB=(t * 3 * H, hd), sC=(t * H, hd))
         wo = ops.cast_bf16(att.output.dense.weight)
         ao = lin(ctxv, wo, att.output.dense.bias, att.output.dense.weight)
-        if pk is None:
-            def add_ln(u, r, ln, s_):
-                return ops.add_ln_fwd(u, r, ln.weight, ln.bias, lyr.eps, ph, seed, s_)
-        else:
-            def add_ln(u, r, ln, s_):
-                return ops.add_ln_rows_fwd(u, r, pk.row_map, ln.weight, ln.bias, lyr.eps, ph, seed, s_)
-        a, mean1, rstd1 = add_ln(ao, x, att.output.LayerNorm, sid + 1)
+        row_map = None if pk is None else pk.row_map
+        ln1, ln2 = att.output.LayerNorm, lyr.output.LayerNorm
+        a, mean1, rstd1 = ops.add_ln_fwd(ao, x, ln1.weight, ln1.bias, lyr.eps, ph, seed, sid + 1, row_map=row_map)
         wi = ops.cast_bf16(lyr.intermediate.dense.weight)
         h1 = lin(a, wi, lyr.intermediate.dense.bias, lyr.intermediate.dense.weight)
         hg = ops.gelu_fwd(h1)
         w2 = ops.cast_bf16(lyr.output.dense.weight)
         o = lin(hg, w2, lyr.output.dense.bias, lyr.output.dense.weight)
-        y, mean2, rstd2 = add_ln(o, a, lyr.output.LayerNorm, sid + 2)
+        y, mean2, rstd2 = ops.add_ln_fwd(o, a, ln2.weight, ln2.bias, lyr.eps, ph, seed, sid + 2, row_map=row_map)
         ctx.lyr, ctx.cfg, ctx.pk = lyr, (b, t, seed, pa, ph, sid), pk
         # hg = gelu(h1) is kept for the FFN2 weight gradient (100 MB per layer at 16384 rows: memory is not the constraint
         # of the text side, a recomputing GELU pass per layer and backward was)
@@ -178,14 +155,10 @@ class _LayerFn(torch.autograd.Function):
         dy = dy.contiguous()
         g = {}
         pk = ctx.pk
-        if pk is None:
-            add_ln_bwd = ops.add_ln_bwd
-        else:
-            def add_ln_bwd(dy_, u, r, gamma, mean, rstd, p_, seed_, s_):
-                return ops.add_ln_rows_bwd(dy_, u, r, pk.row_map, gamma, mean, rstd, p_, seed_, s_)
+        row_map = None if pk is None else pk.row_map
         # y = LN2(dropout(o) + a)
-        do, da_res, g["output.LayerNorm.weight"], g["output.LayerNorm.bias"] = add_ln_bwd(
-            dy, sv["o"], a, lyr.output.LayerNorm.weight, sv["ln2"][0], sv["ln2"][1], ph, seed, sid + 2)
+        do, da_res, g["output.LayerNorm.weight"], g["output.LayerNorm.bias"] = ops.add_ln_bwd(
+            dy, sv["o"], a, lyr.output.LayerNorm.weight, sv["ln2"][0], sv["ln2"][1], ph, seed, sid + 2, row_map=row_map)
         hg = sv.pop("hg")
         g["output.dense.weight"] = ops.linear_wgrad(do, hg)
         g["output.dense.bias"] = ops.colsum(do)
@@ -198,8 +171,8 @@ class _LayerFn(torch.autograd.Function):
         da = ops.linear_dgrad(dh1, sv["wi"], residual=da_res, w_t=ops.cast_transpose_bf16(lyr.intermediate.dense.weight))
         del dh1, da_res
         # a = LN1(dropout(ao) + x)
-        dao, dx_res, g["attention.output.LayerNorm.weight"], g["attention.output.LayerNorm.bias"] = add_ln_bwd(
-            da, sv["ao"], x, att.output.LayerNorm.weight, sv["ln1"][0], sv["ln1"][1], ph, seed, sid + 1)
+        dao, dx_res, g["attention.output.LayerNorm.weight"], g["attention.output.LayerNorm.bias"] = ops.add_ln_bwd(
+            da, sv["ao"], x, att.output.LayerNorm.weight, sv["ln1"][0], sv["ln1"][1], ph, seed, sid + 1, row_map=row_map)
         g["attention.output.dense.weight"] = ops.linear_wgrad(dao, sv["ctxv"])
         g["attention.output.dense.bias"] = ops.colsum(dao)
         dctx = ops.linear_dgrad(dao, sv["wo"], w_t=ops.cast_transpose_bf16(att.output.dense.weight))
@@ -415,13 +388,12 @@ class BertModelHIP(nn.Module):
         mask = attention_mask.contiguous() if attention_mask is not None else torch.ones_like(ids)
         p = cfg.hidden_dropout_prob if self.training else 0.0
         x = _EmbedFn.apply(emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
-                           emb.LayerNorm.weight, emb.LayerNorm.bias, ids, tt, cfg.layer_norm_eps, p, seed, 15)
+                           emb.LayerNorm.weight, emb.LayerNorm.bias, ids, tt, None, cfg.layer_norm_eps, p, seed, 15)
         maskb = ops.mask_bias(mask)
         for lyr in self.encoder.layer:
             x = lyr(x, maskb, b, t, seed)
         x = x.view(b, t, cfg.hidden_size)
         return {"last_hidden_state": x if t == t0 else x[:, :t0].contiguous()}
-
 
     def _forward_packed(self, input_ids, token_type_ids, pk, return_packed):
         self._calls += 1                                   # the padded path's seed sequence
@@ -430,8 +402,8 @@ class BertModelHIP(nn.Module):
         ids = torch.index_select(input_ids.reshape(-1), 0, pk.src)
         tt = torch.index_select(token_type_ids.reshape(-1), 0, pk.src) if token_type_ids is not None else None
         p = cfg.hidden_dropout_prob if self.training else 0.0
-        x = _EmbedPackedFn.apply(emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
-                                 emb.LayerNorm.weight, emb.LayerNorm.bias, ids, tt, pk, cfg.layer_norm_eps, p, seed, 15)
+        x = _EmbedFn.apply(emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
+                           emb.LayerNorm.weight, emb.LayerNorm.bias, ids, tt, pk, cfg.layer_norm_eps, p, seed, 15)
         for lyr in self.encoder.layer:
             x = lyr(x, None, pk.b, pk.t, seed, pk)
         if return_packed:

@@ -2,7 +2,7 @@
 //     ctx = dropout(softmax(alpha * Q K^T + mask_bias)) V
 // forward and backward in one kernel each -- the [b, heads, T, T] score / probability tensors never reach HBM.
 // [ref: model/modules/text_encoder.py:47-49 -> transformers BertSelfAttention.forward (scores, mask, softmax, dropout,
-//       context); head size 64 (BERT-base), T <= 256 (the reference tokenises to max_length 256), T % 32 == 0]
+//       context); head size 64 (BERT-base), T <= 256 (the reference tokenises to max_length 256)]
 //
 // One 8-wave workgroup per (sequence, head); K and V rows (forward) live in LDS, row-major with a 144-byte stride.
 // A wave owns 16 queries at a time and computes S^T = K Q^T on v_mfma_f32_16x16x32_bf16: with the A-operand ROWS of a
@@ -15,13 +15,91 @@
 // row dots, dQ = dS K; the keep-mask bits and the row dots are parked in LDS); phase B = per-key work in the
 // transposed layout (a lane holds 8 consecutive queries of one key): dK = dS^T Q, dV = Pd^T dO with fp32 accumulators
 // held by the wave that owns the 32 keys -- no atomics, bit-reproducible.
+//
+// The kernels are written once and instantiated for two views of the batch, which are also their argument structs:
+//   padded_view (mc_attn_*): a [b, T] batch, T % 32 == 0, every sequence owns T rows; the additive key bias of an
+//     arbitrary mask is staged in LDS; lse is [b*nh*T][2]; LDS offsets are fixed (TMAX rows).  Every `in_seq` test
+//     below is the constant true here.
+//   packed_view (mc_attn_varlen_*): the b reports of a call are concatenated into one [R, 3H] row matrix, sequence i
+//     owns rows cu_seqlens[i] .. cu_seqlens[i+1]-1 (1 <= len_i <= 256) -- what the padded view computes for a mask
+//     1..10..0, without the padded rows [the reference pads every report to max_length 256
+//     (data/datasets/imagetext.py:217-222) and masks the padding, so the real tokens see exactly this]:
+//   * the key blocks ceil(len / 32) and the query-block loop are per-workgroup values; keys >= len of the last
+//     block are masked in registers (score = finfo.min, probability exactly 0), there is no mask_bias array;
+//   * staging never reads a row at or beyond cu_seqlens[i+1] (the next sequence's, or past the allocation): LDS rows
+//     len .. 32*ceil(len/32)-1 are filled with zeros; lanes of a partial query / key block read the sequence's LAST
+//     row instead of their own and do not store;
+//   * the dropout element index is the one the padded [b, T] layout uses -- ((i*nh + head)*T + query) * T/8 + key/8 with
+//     the caller's padded T -- so one seed drops the same (query, key) pairs as mc_attn_fwd on the padded batch;
+//   * lse is [R, nh, 2];
+//   * the dynamic LDS is sized by the call's longest sequence (332 bytes per key in the backward: 21 KB at 64 tokens,
+//     83 KB at 256), so batches of short reports get more workgroups per CU;
+//   * the grid is issued in the order of ``order`` (sequence indices, longest first, optional): a workgroup costs
+//     O(len^2), and the long ones should not start last;
+//   * rows cu_seqlens[b] .. rows-1 (alignment rows that belong to no sequence) get zeros in ctx / dqkv from the first
+//     workgroups of the grid: weight-gradient GEMMs and column sums read them.
 #include "common_hip.h"
-#include "attn_frag.h"
 #include "../../include/mammoclip_hip.h"
 
 namespace {
 
-struct attn_args {
+constexpr int RS = 144;          // LDS row stride (bytes) of a 64-wide bf16 row: +16 B keeps ds_read_b64_tr_b16 conflict-free
+constexpr int TMAX = 256;
+constexpr int HD = 64;
+constexpr float NEG_MAX = -3.4028234663852886e38f;
+
+typedef __attribute__((ext_vector_type(4))) short s4_t;
+typedef __attribute__((ext_vector_type(8))) short s8_t;
+typedef __attribute__((address_space(3))) s4_t lds_s4_t;
+
+// fragment (index n = col0 + (lane & 15), k = row0 + (lane >> 4) * 8 .. +8) of a row-major [k][n] LDS tile
+__device__ __forceinline__ bf16x8_t tr_frag(const unsigned char* tile, int row0, int col0, int lane) {
+    const int g = lane >> 4, i = lane & 15;
+    const unsigned char* a = tile + (row0 + g * 8 + (i >> 2)) * RS + (col0 + (i & 3) * 4) * 2;
+    s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(a));
+    s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(a + 4 * RS));
+    s8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8_t, v);
+}
+// fragment of the row-major tile whose MFMA row r is tile row base + (r>>2)*8 + (r&3): lanes of a 16-row group end up
+// owning rows base + g*8 + (0..3); the caller adds 4 rows for the second tile of the pair
+__device__ __forceinline__ bf16x8_t perm_frag(const unsigned char* tile, int base, int ks, int lane) {
+    const int g = lane >> 4, i = lane & 15;
+    return *reinterpret_cast<const bf16x8_t*>(tile + (base + (i >> 2) * 8 + (i & 3)) * RS + (ks * 32 + g * 8) * 2);
+}
+__device__ __forceinline__ bf16x8_t as_frag(const float* f) {
+    uint4 v = pack8(f);
+    return __builtin_bit_cast(bf16x8_t, v);
+}
+__device__ __forceinline__ float xor_sum16_32(float v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+// rows [0, len) from global memory; PARTIAL: rows [len, tp) zero (otherwise len == tp)
+template <bool PARTIAL>
+__device__ __forceinline__ void stage_rows(unsigned char* dst, const bf16_t* src, long long ld, int len, int tp, int tid) {
+    for (int idx = tid; idx < tp * 8; idx += 512) {
+        const int row = idx >> 3, ch = idx & 7;
+        const uint4* const s = reinterpret_cast<const uint4*>(src + (long long)row * ld + ch * 8);
+        uint4* const d = reinterpret_cast<uint4*>(dst + row * RS + ch * 16);
+        if (!PARTIAL || row < len) *d = *s;
+        else *d = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// what a workgroup works on: sequence bi, head h (bh = bi*nh + h), rows r0 .. r0+len-1 of the row matrices, tp = len
+// rounded up to 32 (the rows the LDS tiles hold)
+struct seq_t {
+    int bi, h, bh, len, tp;
+    long long r0;
+};
+
+// A view = the kernels' argument struct + what differs between the two layouts: lds_rows (rows of an LDS tile),
+// zero_tail (alignment rows), open (the sequence this workgroup takes; false: nothing to do), stage_bias / bias4 / bias /
+// score (the additive key bias and the score it enters), lse_at (row of lse), PARTIAL (a sequence may end inside a
+// 32-row block: the kernels then clamp rows, mask keys and predicate stores with `in_seq`).
+struct padded_view {
     const bf16_t* qkv;      // [b*t, 3H]: Q | K | V
     const float* maskb;     // [b, t] additive key bias
     const bf16_t* dctx;     // [b*t, H] (backward)
@@ -32,31 +110,96 @@ struct attn_args {
     float alpha, p;
     unsigned long long seed;
     unsigned int sid;
+
+    static constexpr bool PARTIAL = false;      // a sequence never ends inside a 32-row block
+    static constexpr int BIAS_ROWS = TMAX;      // floats of LDS for the key bias
+    __host__ __device__ int lds_rows() const { return TMAX; }
+    __device__ void zero_tail(bf16_t*, int, int) const {}
+    __device__ bool open(seq_t& s) const {
+        s.bh = blockIdx.x;
+        s.bi = s.bh / nh; s.h = s.bh % nh; s.len = s.tp = t;
+        s.r0 = (long long)s.bi * t;
+        return true;
+    }
+    __device__ void stage_bias(float* mb, const seq_t& s, int k) const { mb[k] = maskb[s.r0 + k]; }
+    __device__ float4 bias4(const float* mb, int key0) const { return *reinterpret_cast<const float4*>(mb + key0); }
+    __device__ float bias(const float* mb, int key) const { return mb[key]; }
+    __device__ float score(float qk, float bias) const { return qk * alpha + bias; }
+    __device__ float* lse_at(const seq_t& s, int q) const { return lse + ((long long)s.bh * t + q) * 2; }
 };
 
-template <bool DROP>
-__global__ __launch_bounds__(512) void attn_fwd_k(attn_args a) {
+struct packed_view {
+    const bf16_t* qkv;      // [rows, 3H]: Q | K | V
+    const bf16_t* dctx;     // [rows, H] (backward)
+    bf16_t* ctx;            // [rows, H] (forward)
+    bf16_t* dqkv;           // [rows, 3H] (backward)
+    float* lse;             // [rows, nh][2]: row max, 1 / row sum
+    const int* cu;          // [nseq + 1]
+    const int* order;       // [nseq] or null
+    long long rows;
+    int nseq, tl, t, nh;    // tl: LDS rows (longest sequence rounded up to 32); t: T of the padded layout (dropout index)
+    float alpha, p;
+    unsigned long long seed;
+    unsigned int sid;
+
+    static constexpr bool PARTIAL = true;
+    static constexpr int BIAS_ROWS = 0;
+    __host__ __device__ int lds_rows() const { return tl; }
+    // the first nh workgroups of the grid (one per head): zeros in the head's 64 columns of the alignment rows of m
+    // (leading dimension ld)
+    __device__ void zero_tail(bf16_t* m, int ld, int tid) const {
+        if (blockIdx.x >= (unsigned)nh) return;
+        const long long r_begin = cu[nseq];
+        if (r_begin < 0) return;
+        for (long long idx = tid; idx < (rows - r_begin) * 8; idx += 512)
+            *reinterpret_cast<uint4*>(m + (r_begin + (idx >> 3)) * (long long)ld + blockIdx.x * HD + (idx & 7) * 8) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __device__ bool open(seq_t& s) const {
+        const int oi = blockIdx.x / nh;
+        s.h = blockIdx.x % nh;
+        s.bi = order ? order[oi] : oi;
+        if (s.bi < 0 || s.bi >= nseq) return false;
+        const int r0 = cu[s.bi];
+        s.len = cu[s.bi + 1] - r0;
+        if (s.len < 1 || s.len > tl || r0 < 0 || r0 + s.len > rows) return false;      // malformed cu_seqlens: touch nothing
+        s.tp = (s.len + 31) & ~31;
+        s.r0 = r0; s.bh = s.bi * nh + s.h;
+        return true;
+    }
+    __device__ void stage_bias(float*, const seq_t&, int) const {}
+    __device__ float4 bias4(const float*, int) const { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    __device__ float bias(const float*, int) const { return 0.f; }
+    __device__ float score(float qk, float) const { return qk * alpha; }
+    __device__ float* lse_at(const seq_t& s, int q) const { return lse + ((s.r0 + q) * nh + s.h) * 2; }
+};
+
+template <class V, bool DROP>
+__global__ __launch_bounds__(512) void attn_fwd_k(V a) {
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char* const Ks = smem;
-    unsigned char* const Vs = smem + TMAX * RS;
-    float* const mb = reinterpret_cast<float*>(smem + 2 * TMAX * RS);
+    unsigned char* const Vs = smem + a.lds_rows() * RS;
+    float* const mb = reinterpret_cast<float*>(smem + 2 * a.lds_rows() * RS);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
-    const int t = a.t, nh = a.nh, H = nh * HD, ld = 3 * H;
-    const int bh = blockIdx.x, bi = bh / nh, h = bh % nh;
-    const bf16_t* const base = a.qkv + (long long)bi * t * ld + h * HD;
-    stage_rows(Ks, base + H, ld, t, tid);
-    stage_rows(Vs, base + 2 * H, ld, t, tid);
-    for (int k = tid; k < t; k += 512) mb[k] = a.maskb[(long long)bi * t + k];
+    const int nh = a.nh, H = nh * HD, ld = 3 * H;
+    a.zero_tail(a.ctx, H, tid);
+    seq_t sq;
+    if (!a.open(sq)) return;
+    const int h = sq.h, len = sq.len;
+    const auto in_seq = [len](int r) { return !V::PARTIAL || r < len; };
+    const bf16_t* const base = a.qkv + sq.r0 * ld + h * HD;
+    stage_rows<V::PARTIAL>(Ks, base + H, ld, len, sq.tp, tid);
+    stage_rows<V::PARTIAL>(Vs, base + 2 * H, ld, len, sq.tp, tid);
+    for (int k = tid; k < sq.tp; k += 512) a.stage_bias(mb, sq, k);
     __syncthreads();
-    const int nJ = t >> 5;
-    for (int qb = wave; qb * 16 < t; qb += 8) {
-        const int q = qb * 16 + li;
+    const int nJ = sq.tp >> 5;
+    for (int qb = wave; qb * 16 < len; qb += 8) {
+        const int q = qb * 16 + li, qc = in_seq(q) ? q : len - 1;
         bf16x8_t qf[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
-            qf[ks] = *reinterpret_cast<const bf16x8_t*>(base + (long long)q * ld + ks * 32 + g * 8);
+            qf[ks] = *reinterpret_cast<const bf16x8_t*>(base + (long long)qc * ld + ks * 32 + g * 8);
         float s[8][8];
-        float mx = -3.4028234663852886e38f;
+        float mx = NEG_MAX;
 #pragma unroll
         for (int J = 0; J < 8; ++J) {
             if (J < nJ) {
@@ -66,11 +209,12 @@ __global__ __launch_bounds__(512) void attn_fwd_k(attn_args a) {
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks)
                         acc = MC_MFMA_16x16x32(perm_frag(Ks, 32 * J + 4 * tt, ks, lane), qf[ks], acc, 0, 0, 0);
-                    const float4 bv = *reinterpret_cast<const float4*>(mb + 32 * J + g * 8 + 4 * tt);
-                    s[J][tt * 4 + 0] = acc[0] * a.alpha + bv.x;
-                    s[J][tt * 4 + 1] = acc[1] * a.alpha + bv.y;
-                    s[J][tt * 4 + 2] = acc[2] * a.alpha + bv.z;
-                    s[J][tt * 4 + 3] = acc[3] * a.alpha + bv.w;
+                    const int key = 32 * J + g * 8 + 4 * tt;
+                    const float4 bv = a.bias4(mb, key);
+                    s[J][tt * 4 + 0] = in_seq(key + 0) ? a.score(acc[0], bv.x) : NEG_MAX;
+                    s[J][tt * 4 + 1] = in_seq(key + 1) ? a.score(acc[1], bv.y) : NEG_MAX;
+                    s[J][tt * 4 + 2] = in_seq(key + 2) ? a.score(acc[2], bv.z) : NEG_MAX;
+                    s[J][tt * 4 + 3] = in_seq(key + 3) ? a.score(acc[3], bv.w) : NEG_MAX;
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i) mx = fmaxf(mx, s[J][i]);
@@ -85,8 +229,8 @@ __global__ __launch_bounds__(512) void attn_fwd_k(attn_args a) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { s[J][i] = __expf(s[J][i] - mx); sum += s[J][i]; }
         const float inv = 1.f / xor_sum16_32(sum);
-        const long long row = (long long)bh * t + q;
-        if (g == 0) *reinterpret_cast<float2*>(a.lse + row * 2) = make_float2(mx, inv);
+        const long long prow = (long long)sq.bh * a.t + qc;      // row of the padded [b, nh, T, T] probabilities
+        if (g == 0 && in_seq(q)) *reinterpret_cast<float2*>(a.lse_at(sq, q)) = make_float2(mx, inv);
         f32x4_t o[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -98,7 +242,7 @@ __global__ __launch_bounds__(512) void attn_fwd_k(attn_args a) {
                 for (int i = 0; i < 8; ++i) v[i] = s[J][i] * inv;
                 if (DROP) {
                     float ds[8];
-                    dropout_scale8(a.seed, a.sid, (unsigned long long)row * (t >> 3) + 4 * J + g, a.p, ds);
+                    dropout_scale8(a.seed, a.sid, (unsigned long long)prow * (a.t >> 3) + 4 * J + g, a.p, ds);
 #pragma unroll
                     for (int i = 0; i < 8; ++i) v[i] *= ds[i];
                 }
@@ -108,48 +252,59 @@ __global__ __launch_bounds__(512) void attn_fwd_k(attn_args a) {
                     o[dt] = MC_MFMA_16x16x32(tr_frag(Vs, 32 * J, dt * 16, lane), pf, o[dt], 0, 0, 0);
             }
         }
-        bf16_t* const dst = a.ctx + ((long long)bi * t + q) * H + h * HD + g * 4;
+        if (in_seq(q)) {
+            bf16_t* const dst = a.ctx + (sq.r0 + q) * H + h * HD + g * 4;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-            *reinterpret_cast<uint2*>(dst + dt * 16) = make_uint2(pack_bf2(o[dt][0], o[dt][1]), pack_bf2(o[dt][2], o[dt][3]));
+            for (int dt = 0; dt < 4; ++dt)
+                *reinterpret_cast<uint2*>(dst + dt * 16) = make_uint2(pack_bf2(o[dt][0], o[dt][1]), pack_bf2(o[dt][2], o[dt][3]));
+        }
     }
 }
 
-template <bool DROP>
-__global__ __launch_bounds__(512) void attn_bwd_k(attn_args a) {
+template <class V, bool DROP>
+__global__ __launch_bounds__(512) void attn_bwd_k(V a) {
     extern __shared__ __align__(16) unsigned char smem[];
+    const int tl = a.lds_rows();
     unsigned char* const Ks = smem;                    // phase A: K rows, phase B: Q rows
-    unsigned char* const Vs = smem + TMAX * RS;        // phase A: V rows, phase B: dO rows
-    float* const mb = reinterpret_cast<float*>(smem + 2 * TMAX * RS);
-    float* const lse_s = mb + TMAX;                    // [t][2]
-    float* const dot_s = lse_s + 2 * TMAX;             // [t]
-    unsigned char* const dmask = reinterpret_cast<unsigned char*>(dot_s + TMAX);   // [t][32] keep bits, 8 keys per byte
+    unsigned char* const Vs = smem + tl * RS;          // phase A: V rows, phase B: dO rows
+    float* const mb = reinterpret_cast<float*>(smem + 2 * tl * RS);
+    float* const lse_s = mb + V::BIAS_ROWS;            // [tl][2]
+    float* const dot_s = lse_s + 2 * tl;               // [tl]
+    unsigned char* const dmask = reinterpret_cast<unsigned char*>(dot_s + tl);     // [tl][32] keep bits, 8 keys per byte
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
-    const int t = a.t, nh = a.nh, H = nh * HD, ld = 3 * H;
-    const int bh = blockIdx.x, bi = bh / nh, h = bh % nh;
-    const bf16_t* const base = a.qkv + (long long)bi * t * ld + h * HD;
-    const bf16_t* const dbase = a.dctx + (long long)bi * t * H + h * HD;
-    bf16_t* const gbase = a.dqkv + (long long)bi * t * ld + h * HD;
-    stage_rows(Ks, base + H, ld, t, tid);
-    stage_rows(Vs, base + 2 * H, ld, t, tid);
-    for (int k = tid; k < t; k += 512) {
-        mb[k] = a.maskb[(long long)bi * t + k];
-        *reinterpret_cast<float2*>(lse_s + 2 * k) = *reinterpret_cast<const float2*>(a.lse + ((long long)bh * t + k) * 2);
+    const int nh = a.nh, H = nh * HD, ld = 3 * H;
+#pragma unroll
+    for (int part = 0; part < 3; ++part) a.zero_tail(a.dqkv + part * H, ld, tid);
+    seq_t sq;
+    if (!a.open(sq)) return;
+    const int h = sq.h, len = sq.len;
+    const auto in_seq = [len](int r) { return !V::PARTIAL || r < len; };
+    const bf16_t* const base = a.qkv + sq.r0 * ld + h * HD;
+    const bf16_t* const dbase = a.dctx + sq.r0 * H + h * HD;
+    bf16_t* const gbase = a.dqkv + sq.r0 * ld + h * HD;
+    stage_rows<V::PARTIAL>(Ks, base + H, ld, len, sq.tp, tid);
+    stage_rows<V::PARTIAL>(Vs, base + 2 * H, ld, len, sq.tp, tid);
+    for (int k = tid; k < sq.tp; k += 512) {
+        a.stage_bias(mb, sq, k);
+        float2 l2 = make_float2(0.f, 0.f);
+        if (in_seq(k)) l2 = *reinterpret_cast<const float2*>(a.lse_at(sq, k));
+        *reinterpret_cast<float2*>(lse_s + 2 * k) = l2;
+        if (V::PARTIAL) dot_s[k] = 0.f;                // phase A writes only the rows < len
     }
     __syncthreads();
-    const int nJ = t >> 5;
+    const int nJ = sq.tp >> 5;
     const float invkeep = 1.f / (1.f - a.p);
     // ---------------- phase A: a lane = one query x 8 consecutive keys per 32-key block
-    for (int qb = wave; qb * 16 < t; qb += 8) {
-        const int q = qb * 16 + li;
+    for (int qb = wave; qb * 16 < len; qb += 8) {
+        const int q = qb * 16 + li, qc = in_seq(q) ? q : len - 1;
         bf16x8_t qf[2], dof[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            qf[ks] = *reinterpret_cast<const bf16x8_t*>(base + (long long)q * ld + ks * 32 + g * 8);
-            dof[ks] = *reinterpret_cast<const bf16x8_t*>(dbase + (long long)q * H + ks * 32 + g * 8);
+            qf[ks] = *reinterpret_cast<const bf16x8_t*>(base + (long long)qc * ld + ks * 32 + g * 8);
+            dof[ks] = *reinterpret_cast<const bf16x8_t*>(dbase + (long long)qc * H + ks * 32 + g * 8);
         }
-        const float mx = lse_s[2 * q], inv = lse_s[2 * q + 1];
-        const long long row = (long long)bh * t + q;
+        const float mx = lse_s[2 * qc], inv = lse_s[2 * qc + 1];
+        const long long prow = (long long)sq.bh * a.t + qc;      // row of the padded [b, nh, T, T] probabilities
         float pr[8][8], d[8][8];
         float dot = 0.f;
 #pragma unroll
@@ -163,32 +318,33 @@ __global__ __launch_bounds__(512) void attn_bwd_k(attn_args a) {
                         acc = MC_MFMA_16x16x32(perm_frag(Ks, 32 * J + 4 * tt, ks, lane), qf[ks], acc, 0, 0, 0);
                         dacc = MC_MFMA_16x16x32(perm_frag(Vs, 32 * J + 4 * tt, ks, lane), dof[ks], dacc, 0, 0, 0);
                     }
-                    const float4 bv = *reinterpret_cast<const float4*>(mb + 32 * J + g * 8 + 4 * tt);
+                    const int key = 32 * J + g * 8 + 4 * tt;
+                    const float4 bv = a.bias4(mb, key);
                     const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float v = __expf(acc[r] * a.alpha + bb[r] - mx) * inv;
+                        const float v = in_seq(key + r) ? __expf(a.score(acc[r], bb[r]) - mx) * inv : 0.f;
                         pr[J][tt * 4 + r] = bf2f(f2bf(v));
                         d[J][tt * 4 + r] = dacc[r];
                     }
                 }
                 if (DROP) {
                     float ds[8];
-                    dropout_scale8(a.seed, a.sid, (unsigned long long)row * (t >> 3) + 4 * J + g, a.p, ds);
+                    dropout_scale8(a.seed, a.sid, (unsigned long long)prow * (a.t >> 3) + 4 * J + g, a.p, ds);
                     unsigned int bits = 0;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         d[J][i] *= ds[i];
                         bits |= (ds[i] != 0.f ? 1u : 0u) << i;
                     }
-                    dmask[q * 32 + 4 * J + g] = (unsigned char)bits;
+                    if (in_seq(q)) dmask[q * 32 + 4 * J + g] = (unsigned char)bits;
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i) dot += pr[J][i] * d[J][i];
             }
         }
         dot = xor_sum16_32(dot);
-        if (g == 0) dot_s[q] = dot;
+        if (g == 0 && in_seq(q)) dot_s[q] = dot;
         f32x4_t dq[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -204,28 +360,30 @@ __global__ __launch_bounds__(512) void attn_bwd_k(attn_args a) {
                     dq[dt] = MC_MFMA_16x16x32(tr_frag(Ks, 32 * J, dt * 16, lane), dsf, dq[dt], 0, 0, 0);
             }
         }
-        bf16_t* const dst = gbase + (long long)q * ld + g * 4;
+        if (in_seq(q)) {
+            bf16_t* const dst = gbase + (long long)q * ld + g * 4;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-            *reinterpret_cast<uint2*>(dst + dt * 16) = make_uint2(pack_bf2(dq[dt][0], dq[dt][1]), pack_bf2(dq[dt][2], dq[dt][3]));
+            for (int dt = 0; dt < 4; ++dt)
+                *reinterpret_cast<uint2*>(dst + dt * 16) = make_uint2(pack_bf2(dq[dt][0], dq[dt][1]), pack_bf2(dq[dt][2], dq[dt][3]));
+        }
     }
     __syncthreads();
     // ---------------- phase B: a lane = one key x 8 consecutive queries per 32-query block; a wave owns 32 keys
-    stage_rows(Ks, base, ld, t, tid);          // Q rows
-    stage_rows(Vs, dbase, H, t, tid);          // dO rows
+    stage_rows<V::PARTIAL>(Ks, base, ld, len, sq.tp, tid);          // Q rows
+    stage_rows<V::PARTIAL>(Vs, dbase, H, len, sq.tp, tid);          // dO rows
     __syncthreads();
-    if (wave * 32 >= t) return;
+    if (wave * 32 >= len) return;
     bf16x8_t kfr[2][2], vfr[2][2];
     float mbk[2];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
-        const int key = wave * 32 + kt * 16 + li;
+        const int key = wave * 32 + kt * 16 + li, kc = in_seq(key) ? key : len - 1;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            kfr[kt][ks] = *reinterpret_cast<const bf16x8_t*>(base + H + (long long)key * ld + ks * 32 + g * 8);
-            vfr[kt][ks] = *reinterpret_cast<const bf16x8_t*>(base + 2 * H + (long long)key * ld + ks * 32 + g * 8);
+            kfr[kt][ks] = *reinterpret_cast<const bf16x8_t*>(base + H + (long long)kc * ld + ks * 32 + g * 8);
+            vfr[kt][ks] = *reinterpret_cast<const bf16x8_t*>(base + 2 * H + (long long)kc * ld + ks * 32 + g * 8);
         }
-        mbk[kt] = mb[key];
+        mbk[kt] = a.bias(mb, key);
     }
     f32x4_t dk[2][4], dv[2][4];
 #pragma unroll
@@ -273,7 +431,8 @@ __global__ __launch_bounds__(512) void attn_bwd_k(attn_args a) {
             float pdv[8], dsv[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float v = __expf(sv[kt][i] * a.alpha + mbk[kt] - ls[2 * i]) * ls[2 * i + 1];
+                // a query row >= len (zero Q / dO rows in LDS) contributes nothing to dK / dV
+                const float v = in_seq(q0 + i) ? __expf(a.score(sv[kt][i], mbk[kt]) - ls[2 * i]) * ls[2 * i + 1] : 0.f;
                 const float prr = bf2f(f2bf(v));
                 float dsc = 1.f;
                 if (DROP) dsc = ((dmask[(q0 + i) * 32 + (key >> 3)] >> (key & 7)) & 1) ? invkeep : 0.f;
@@ -297,6 +456,7 @@ __global__ __launch_bounds__(512) void attn_bwd_k(attn_args a) {
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
         const int key = wave * 32 + kt * 16 + li;
+        if (!in_seq(key)) continue;                    // a column of the accumulators that belongs to no key
         bf16_t* const dst = gbase + (long long)key * ld + g * 4;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
@@ -308,12 +468,34 @@ __global__ __launch_bounds__(512) void attn_bwd_k(attn_args a) {
     }
 }
 
-constexpr int FWD_LDS = 2 * TMAX * RS + TMAX * 4;
-constexpr int BWD_LDS = 2 * TMAX * RS + TMAX * 4 * 4 + TMAX * 32;
+// dynamic LDS of a workgroup whose tiles hold tl rows: K/V tiles, the view's key bias, backward: lse, row dots, keep bits
+template <class V, bool BWD>
+constexpr int lds_bytes(int tl) { return 2 * tl * RS + V::BIAS_ROWS * 4 + (BWD ? tl * 4 * 3 + tl * 32 : 0); }
+
+// one workgroup per (sequence, head), with or without dropout
+template <class V, bool BWD>
+int launch(const V& a, int nseq, void* stream) {
+    constexpr auto drop = BWD ? attn_bwd_k<V, true> : attn_fwd_k<V, true>;
+    constexpr auto nodrop = BWD ? attn_bwd_k<V, false> : attn_fwd_k<V, false>;
+    static unsigned long long done_t = 0, done_f = 0;
+    MC_SET_MAX_LDS(done_t, drop, (lds_bytes<V, BWD>(TMAX)));
+    MC_SET_MAX_LDS(done_f, nodrop, (lds_bytes<V, BWD>(TMAX)));
+    hipLaunchKernelGGL(a.p > 0.f ? drop : nodrop, dim3(nseq * a.nh), dim3(512), (lds_bytes<V, BWD>(a.lds_rows())), (hipStream_t)stream, a);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
 
 int check_shape(int b, int t, int nh, float p) {
     MC_CHECK(b > 0 && nh > 0 && t >= 32 && t <= TMAX && t % 32 == 0, "attn: needs 32 <= t <= 256, t % 32 == 0 (head size 64)");
     MC_CHECK(p >= 0.f && p < 1.f, "attn: dropout p out of range");
+    return MC_OK;
+}
+
+int check_shape_varlen(int b, int max_len, int t_pad, long long rows, int nh, float p) {
+    MC_CHECK(b > 0 && nh > 0 && max_len >= 1 && max_len <= TMAX, "attn_varlen: needs 1 <= max_len <= 256 (head size 64)");
+    MC_CHECK(t_pad >= max_len && t_pad % 8 == 0, "attn_varlen: t_pad (the padded layout's T) must be >= max_len and a multiple of 8");
+    MC_CHECK(rows >= b && rows <= 0x7fffffffLL, "attn_varlen: bad row count");
+    MC_CHECK(p >= 0.f && p < 1.f, "attn_varlen: dropout p out of range");
     return MC_OK;
 }
 
@@ -325,16 +507,10 @@ extern "C" int mc_attn_fwd(const mc_bf16* qkv, const float* mask_bias, int b, in
                            unsigned long long seed, unsigned int stream_id, mc_bf16* ctx, float* lse, void* stream) {
     MC_CHECK(qkv && mask_bias && ctx && lse, "attn_fwd: null pointer");
     if (int e = check_shape(b, t, nh, p)) return e;
-    attn_args a{};
+    padded_view a{};
     a.qkv = (const bf16_t*)qkv; a.maskb = mask_bias; a.ctx = (bf16_t*)ctx; a.lse = lse;
     a.t = t; a.nh = nh; a.alpha = alpha; a.p = p; a.seed = seed; a.sid = stream_id;
-    static unsigned long long done_t = 0, done_f = 0;
-    MC_SET_MAX_LDS(done_t, attn_fwd_k<true>, FWD_LDS);
-    MC_SET_MAX_LDS(done_f, attn_fwd_k<false>, FWD_LDS);
-    if (p > 0.f) hipLaunchKernelGGL(attn_fwd_k<true>, dim3(b * nh), dim3(512), FWD_LDS, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(attn_fwd_k<false>, dim3(b * nh), dim3(512), FWD_LDS, (hipStream_t)stream, a);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch<padded_view, false>(a, b, stream);
 }
 
 extern "C" int mc_attn_bwd(const mc_bf16* qkv, const float* mask_bias, const mc_bf16* dctx, const float* lse, int b, int t,
@@ -342,15 +518,36 @@ extern "C" int mc_attn_bwd(const mc_bf16* qkv, const float* mask_bias, const mc_
                            void* stream) {
     MC_CHECK(qkv && mask_bias && dctx && lse && dqkv, "attn_bwd: null pointer");
     if (int e = check_shape(b, t, nh, p)) return e;
-    attn_args a{};
+    padded_view a{};
     a.qkv = (const bf16_t*)qkv; a.maskb = mask_bias; a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv;
     a.lse = const_cast<float*>(lse);
     a.t = t; a.nh = nh; a.alpha = alpha; a.p = p; a.seed = seed; a.sid = stream_id;
-    static unsigned long long done_t = 0, done_f = 0;
-    MC_SET_MAX_LDS(done_t, attn_bwd_k<true>, BWD_LDS);
-    MC_SET_MAX_LDS(done_f, attn_bwd_k<false>, BWD_LDS);
-    if (p > 0.f) hipLaunchKernelGGL(attn_bwd_k<true>, dim3(b * nh), dim3(512), BWD_LDS, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(attn_bwd_k<false>, dim3(b * nh), dim3(512), BWD_LDS, (hipStream_t)stream, a);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch<padded_view, true>(a, b, stream);
+}
+
+extern "C" int mc_attn_varlen_supported(int max_len, int head_dim) { return head_dim == HD && max_len >= 1 && max_len <= TMAX; }
+
+extern "C" int mc_attn_varlen_fwd(const mc_bf16* qkv, const int* cu_seqlens, const int* order, int b, int max_len, int t_pad,
+                                  long long rows, int nh, float alpha, float p, unsigned long long seed,
+                                  unsigned int stream_id, mc_bf16* ctx, float* lse, void* stream) {
+    MC_CHECK(qkv && cu_seqlens && ctx && lse, "attn_varlen_fwd: null pointer");
+    if (int e = check_shape_varlen(b, max_len, t_pad, rows, nh, p)) return e;
+    packed_view a{};
+    a.qkv = (const bf16_t*)qkv; a.ctx = (bf16_t*)ctx; a.lse = lse; a.cu = cu_seqlens; a.order = order;
+    a.rows = rows; a.nseq = b; a.tl = (max_len + 31) & ~31; a.t = t_pad; a.nh = nh;
+    a.alpha = alpha; a.p = p; a.seed = seed; a.sid = stream_id;
+    return launch<packed_view, false>(a, b, stream);
+}
+
+extern "C" int mc_attn_varlen_bwd(const mc_bf16* qkv, const int* cu_seqlens, const int* order, const mc_bf16* dctx,
+                                  const float* lse, int b, int max_len, int t_pad, long long rows, int nh, float alpha,
+                                  float p, unsigned long long seed, unsigned int stream_id, mc_bf16* dqkv, void* stream) {
+    MC_CHECK(qkv && cu_seqlens && dctx && lse && dqkv, "attn_varlen_bwd: null pointer");
+    if (int e = check_shape_varlen(b, max_len, t_pad, rows, nh, p)) return e;
+    packed_view a{};
+    a.qkv = (const bf16_t*)qkv; a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv; a.lse = const_cast<float*>(lse);
+    a.cu = cu_seqlens; a.order = order;
+    a.rows = rows; a.nseq = b; a.tl = (max_len + 31) & ~31; a.t = t_pad; a.nh = nh;
+    a.alpha = alpha; a.p = p; a.seed = seed; a.sid = stream_id;
+    return launch<packed_view, true>(a, b, stream);
 }

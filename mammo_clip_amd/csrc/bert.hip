@@ -538,6 +538,44 @@ int row_blocks(long long rows) {
     return (int)b;
 }
 
+// embedding backward over t positions of b sequences; cu_seqlens set: packed rows, dropout indices of the [b, t_pad] layout
+int launch_embed_bwd(const mc_bf16* dy, const long long* ids, const long long* tt, const int* cu_seqlens, const float* word,
+                     const float* pos, const float* type, const float* gamma, const float* mean, const float* rstd, int b, int t,
+                     int t_pad, int h, float p, unsigned long long seed, unsigned int stream_id, float* dword, float* dpos,
+                     float* dtype, float* dgamma, float* dbeta, void* stream) {
+    int nbw = 2048 / t;
+    if (nbw < 1) nbw = 1;
+    if (nbw > b) nbw = b;
+    long long waves = (long long)t * nbw;
+    hipLaunchKernelGGL(cu_seqlens ? embed_bwd_k<true> : embed_bwd_k<false>, dim3(mc_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream,
+                       dy, ids, cu_seqlens, t_pad, tt, word, pos, type, gamma, mean, rstd, b, t, h, nbw, p, seed, stream_id, dword, dpos,
+                       dtype, dgamma, dbeta);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+// the two add+LayerNorm entry points (padded rows / row_map of the packed layout) differ in row_map only
+int launch_add_ln_fwd(const char* shape_msg, const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma,
+                      const float* beta, float eps, long long rows, int h, float p, unsigned long long seed,
+                      unsigned int stream_id, mc_bf16* y, float* mean, float* rstd, void* stream) {
+    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, shape_msg);
+    hipLaunchKernelGGL(row_map ? add_ln_fwd_k<true> : add_ln_fwd_k<false>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream,
+                       x, res, row_map, gamma, beta, eps, rows, h, p, seed, stream_id, y, mean, rstd);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+int launch_add_ln_bwd(const char* shape_msg, const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map,
+                      const float* gamma, const float* mean, const float* rstd, long long rows, int h, float p,
+                      unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres, float* dgamma,
+                      float* dbeta, void* stream) {
+    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, shape_msg);
+    long long blocks = (rows + 3) / 4;
+    if (blocks > 512) blocks = 512;
+    hipLaunchKernelGGL(row_map ? add_ln_bwd_k<true> : add_ln_bwd_k<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy,
+                       x, res, row_map, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres, dgamma, dbeta);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
 }  // namespace
 
 extern "C" int mc_bert_embed_fwd(const long long* ids, const long long* tt, const float* word, const float* pos,
@@ -559,37 +597,22 @@ extern "C" int mc_bert_embed_bwd(const mc_bf16* dy, const long long* ids, const 
                                  float* dbeta, void* stream) {
     MC_CHECK(dy && ids && word && pos && type && gamma && mean && rstd && dword && dpos && dtype && dgamma && dbeta, "embed_bwd: null arg");
     MC_CHECK(b > 0 && t > 0 && h > 0 && h % 8 == 0 && h <= 1024, "embed_bwd: bad shape");
-    int nbw = 2048 / t;
-    if (nbw < 1) nbw = 1;
-    if (nbw > b) nbw = b;
-    long long waves = (long long)t * nbw;
-    hipLaunchKernelGGL(embed_bwd_k<false>, dim3(mc_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream, dy, ids, nullptr, t, tt,
-                       word, pos, type, gamma, mean, rstd, b, t, h, nbw, p, seed, stream_id, dword, dpos, dtype, dgamma, dbeta);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch_embed_bwd(dy, ids, tt, nullptr, word, pos, type, gamma, mean, rstd, b, t, t, h, p, seed, stream_id, dword, dpos, dtype,
+                            dgamma, dbeta, stream);
 }
 extern "C" int mc_add_ln_fwd(const mc_bf16* x, const mc_bf16* res, const float* gamma, const float* beta, float eps,
                              long long rows, int h, float p, unsigned long long seed, unsigned int stream_id, mc_bf16* y,
                              float* mean, float* rstd, void* stream) {
     MC_CHECK(x && res && gamma && beta && y && mean && rstd, "add_ln_fwd: null arg");
-    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_fwd: bad shape");
-    hipLaunchKernelGGL(add_ln_fwd_k<false>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, res, nullptr, gamma,
-                       beta, eps, rows, h, p, seed, stream_id, y, mean, rstd);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch_add_ln_fwd("add_ln_fwd: bad shape", x, res, nullptr, gamma, beta, eps, rows, h, p, seed, stream_id, y, mean, rstd, stream);
 }
 extern "C" int mc_add_ln_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const float* gamma,
                              const float* mean, const float* rstd, long long rows, int h, float p,
                              unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres, float* dgamma,
                              float* dbeta, void* stream) {
     MC_CHECK(dy && x && res && gamma && mean && rstd && dx && dres && dgamma && dbeta, "add_ln_bwd: null arg");
-    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_bwd: bad shape");
-    long long blocks = (rows + 3) / 4;
-    if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(add_ln_bwd_k<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy, x, res, nullptr, gamma, mean,
-                       rstd, rows, h, p, seed, stream_id, dx, dres, dgamma, dbeta);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch_add_ln_bwd("add_ln_bwd: bad shape", dy, x, res, nullptr, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres, dgamma,
+                             dbeta, stream);
 }
 extern "C" int mc_softmax_fwd(const float* scores, long long rows, int t, float p, unsigned long long seed,
                               unsigned int stream_id, mc_bf16* probs, mc_bf16* probs_drop, void* stream) {
@@ -738,38 +761,23 @@ extern "C" int mc_bert_embed_rows_bwd(const mc_bf16* dy, const long long* ids, c
     MC_CHECK(dy && ids && cu_seqlens && word && pos && type && gamma && mean && rstd && dword && dpos && dtype && dgamma && dbeta,
              "embed_rows_bwd: null arg");
     MC_CHECK(b > 0 && max_len > 0 && t_pad >= max_len && h > 0 && h % 8 == 0 && h <= 1024, "embed_rows_bwd: bad shape");
-    int nbw = 2048 / max_len;
-    if (nbw < 1) nbw = 1;
-    if (nbw > b) nbw = b;
-    long long waves = (long long)max_len * nbw;
-    hipLaunchKernelGGL(embed_bwd_k<true>, dim3(mc_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream, dy, ids, cu_seqlens, t_pad,
-                       tt, word, pos, type, gamma, mean, rstd, b, max_len, h, nbw, p, seed, stream_id, dword, dpos, dtype,
-                       dgamma, dbeta);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch_embed_bwd(dy, ids, tt, cu_seqlens, word, pos, type, gamma, mean, rstd, b, max_len, t_pad, h, p, seed, stream_id, dword,
+                            dpos, dtype, dgamma, dbeta, stream);
 }
 extern "C" int mc_add_ln_rows_fwd(const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma,
                                   const float* beta, float eps, long long rows, int h, float p, unsigned long long seed,
                                   unsigned int stream_id, mc_bf16* y, float* mean, float* rstd, void* stream) {
     MC_CHECK(x && res && row_map && gamma && beta && y && mean && rstd, "add_ln_rows_fwd: null arg");
-    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_rows_fwd: bad shape");
-    hipLaunchKernelGGL(add_ln_fwd_k<true>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, res, row_map, gamma,
-                       beta, eps, rows, h, p, seed, stream_id, y, mean, rstd);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch_add_ln_fwd("add_ln_rows_fwd: bad shape", x, res, row_map, gamma, beta, eps, rows, h, p, seed, stream_id, y, mean, rstd,
+                             stream);
 }
 extern "C" int mc_add_ln_rows_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map,
                                   const float* gamma, const float* mean, const float* rstd, long long rows, int h, float p,
                                   unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres,
                                   float* dgamma, float* dbeta, void* stream) {
     MC_CHECK(dy && x && res && row_map && gamma && mean && rstd && dx && dres && dgamma && dbeta, "add_ln_rows_bwd: null arg");
-    MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, "add_ln_rows_bwd: bad shape");
-    long long blocks = (rows + 3) / 4;
-    if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(add_ln_bwd_k<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy, x, res, row_map, gamma, mean,
-                       rstd, rows, h, p, seed, stream_id, dx, dres, dgamma, dbeta);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return launch_add_ln_bwd("add_ln_rows_bwd: bad shape", dy, x, res, row_map, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres,
+                             dgamma, dbeta, stream);
 }
 extern "C" int mc_rows_gather(const mc_bf16* src, const int* idx, int n, int h, float* out, void* stream) {
     MC_CHECK(src && idx && out && n > 0 && h > 0, "rows_gather: bad args");

@@ -1011,44 +1011,57 @@ def dropout_f32(x, p, seed, stream_id):
 
 
 # ------------------------------------------------------------------------------------------- BERT pieces
-def bert_embed_fwd(ids, tt, word, pos, typ, gamma, beta, eps, p, seed, sid):
-    b, t = ids.shape
+def bert_embed_fwd(ids, tt, word, pos, typ, gamma, beta, eps, p, seed, sid, pk=None):
+    """``pk`` (PackedRows) set: ``ids`` / ``tt`` hold the real tokens in packed order, the result has pk.rows rows."""
+    rows = ids.numel() if pk is None else pk.rows
     h = word.shape[1]
-    y = empty((b * t, h), BF16, word)
-    mean = empty((b * t,), torch.float32, word)
-    rstd = empty((b * t,), torch.float32, word)
-    L.call("mc_bert_embed_fwd", _p(ids), _p(tt), _p(word), _p(pos), _p(typ), _p(gamma), _p(beta), eps, b, t, h,
-           float(p), int(seed), int(sid), _p(y), _p(mean), _p(rstd), _st())
+    y = empty((rows, h), BF16, word)
+    mean = empty((rows,), torch.float32, word)
+    rstd = empty((rows,), torch.float32, word)
+    tail = (float(p), int(seed), int(sid), _p(y), _p(mean), _p(rstd), _st())
+    if pk is None:
+        b, t = ids.shape
+        L.call("mc_bert_embed_fwd", _p(ids), _p(tt), _p(word), _p(pos), _p(typ), _p(gamma), _p(beta), eps, b, t, h, *tail)
+    else:
+        L.call("mc_bert_embed_rows_fwd", _p(ids), _p(tt), _p(pk.pos), _p(pk.row_map), _p(word), _p(pos), _p(typ), _p(gamma),
+               _p(beta), eps, rows, h, *tail)
     return y, mean, rstd
 
 
-def bert_embed_bwd(dy, ids, tt, word, pos, typ, gamma, mean, rstd, p, seed, sid):
-    b, t = ids.shape
+def bert_embed_bwd(dy, ids, tt, word, pos, typ, gamma, mean, rstd, p, seed, sid, pk=None):
     h = word.shape[1]
     dword, dpos, dtyp = torch.zeros_like(word), torch.zeros_like(pos), torch.zeros_like(typ)
     dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
-    L.call("mc_bert_embed_bwd", _p(dy), _p(ids), _p(tt), _p(word), _p(pos), _p(typ), _p(gamma), _p(mean), _p(rstd),
-           b, t, h, float(p), int(seed), int(sid), _p(dword), _p(dpos), _p(dtyp), _p(dgamma), _p(dbeta), _st())
+    tail = (h, float(p), int(seed), int(sid), _p(dword), _p(dpos), _p(dtyp), _p(dgamma), _p(dbeta), _st())
+    if pk is None:
+        b, t = ids.shape
+        L.call("mc_bert_embed_bwd", _p(dy), _p(ids), _p(tt), _p(word), _p(pos), _p(typ), _p(gamma), _p(mean), _p(rstd), b, t, *tail)
+    else:
+        L.call("mc_bert_embed_rows_bwd", _p(dy), _p(ids), _p(tt), _p(pk.cu), _p(word), _p(pos), _p(typ), _p(gamma), _p(mean),
+               _p(rstd), pk.b, pk.max_len, pk.t, *tail)
     return dword, dpos, dtyp, dgamma, dbeta
 
 
-def add_ln_fwd(x, res, gamma, beta, eps, p, seed, sid):
+def add_ln_fwd(x, res, gamma, beta, eps, p, seed, sid, row_map=None):
+    """``row_map`` (PackedRows.row_map) set: packed rows, dropout indices of the padded layout."""
     rows, h = x.shape
     y = empty((rows, h), BF16, x)
     mean = empty((rows,), torch.float32, x)
     rstd = empty((rows,), torch.float32, x)
-    L.call("mc_add_ln_fwd", _p(x), _p(res), _p(gamma), _p(beta), eps, rows, h, float(p), int(seed), int(sid), _p(y),
-           _p(mean), _p(rstd), _st())
+    name, rm = ("mc_add_ln_fwd", ()) if row_map is None else ("mc_add_ln_rows_fwd", (_p(row_map),))
+    L.call(name, _p(x), _p(res), *rm, _p(gamma), _p(beta), eps, rows, h, float(p), int(seed), int(sid), _p(y), _p(mean),
+           _p(rstd), _st())
     return y, mean, rstd
 
 
-def add_ln_bwd(dy, x, res, gamma, mean, rstd, p, seed, sid):
+def add_ln_bwd(dy, x, res, gamma, mean, rstd, p, seed, sid, row_map=None):
     rows, h = x.shape
     dx, dres = empty((rows, h), BF16, x), empty((rows, h), BF16, x)
     gb = torch.zeros((2,) + tuple(gamma.shape), dtype=gamma.dtype, device=gamma.device)
     dgamma, dbeta = gb[0], gb[1]
-    L.call("mc_add_ln_bwd", _p(dy), _p(x), _p(res), _p(gamma), _p(mean), _p(rstd), rows, h, float(p), int(seed),
-           int(sid), _p(dx), _p(dres), _p(dgamma), _p(dbeta), _st())
+    name, rm = ("mc_add_ln_bwd", ()) if row_map is None else ("mc_add_ln_rows_bwd", (_p(row_map),))
+    L.call(name, _p(dy), _p(x), _p(res), *rm, _p(gamma), _p(mean), _p(rstd), rows, h, float(p), int(seed), int(sid), _p(dx),
+           _p(dres), _p(dgamma), _p(dbeta), _st())
     return dx, dres, dgamma, dbeta
 
 
@@ -1071,7 +1084,6 @@ def softmax_bwd(probs, dpd, p, seed, sid, alpha):
 
 def attn_supported(t, head_dim):
     """Whether the fused attention kernels take this shape (otherwise: batched GEMM + softmax kernels)."""
-    import os
     if os.environ.get("MC_FUSED_ATTN", "1") == "0":      # developer switch: A/B against the unfused kernels
         return False
     return bool(L.load().mc_attn_supported(int(t), int(head_dim)))
@@ -1203,46 +1215,6 @@ def attn_varlen_bwd(qkv, pk, dctx, lse, nh, alpha, p, seed, sid):
     L.call("mc_attn_varlen_bwd", _p(qkv), _p(pk.cu), _p(pk.order), _p(dctx), _p(lse), pk.b, pk.max_len, pk.t, pk.rows, nh,
            float(alpha), float(p), int(seed), int(sid), _p(dqkv), _st())
     return dqkv
-
-
-def bert_embed_rows_fwd(ids, tt, pk, word, pos, typ, gamma, beta, eps, p, seed, sid):
-    h = word.shape[1]
-    y = empty((pk.rows, h), BF16, word)
-    mean = empty((pk.rows,), torch.float32, word)
-    rstd = empty((pk.rows,), torch.float32, word)
-    L.call("mc_bert_embed_rows_fwd", _p(ids), _p(tt), _p(pk.pos), _p(pk.row_map), _p(word), _p(pos), _p(typ), _p(gamma), _p(beta),
-           eps, pk.rows, h, float(p), int(seed), int(sid), _p(y), _p(mean), _p(rstd), _st())
-    return y, mean, rstd
-
-
-def bert_embed_rows_bwd(dy, ids, tt, pk, word, pos, typ, gamma, mean, rstd, p, seed, sid):
-    h = word.shape[1]
-    dword, dpos, dtyp = torch.zeros_like(word), torch.zeros_like(pos), torch.zeros_like(typ)
-    dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
-    L.call("mc_bert_embed_rows_bwd", _p(dy), _p(ids), _p(tt), _p(pk.cu), _p(word), _p(pos), _p(typ), _p(gamma), _p(mean),
-           _p(rstd), pk.b, pk.max_len, pk.t, h, float(p), int(seed), int(sid), _p(dword), _p(dpos), _p(dtyp), _p(dgamma),
-           _p(dbeta), _st())
-    return dword, dpos, dtyp, dgamma, dbeta
-
-
-def add_ln_rows_fwd(x, res, row_map, gamma, beta, eps, p, seed, sid):
-    rows, h = x.shape
-    y = empty((rows, h), BF16, x)
-    mean = empty((rows,), torch.float32, x)
-    rstd = empty((rows,), torch.float32, x)
-    L.call("mc_add_ln_rows_fwd", _p(x), _p(res), _p(row_map), _p(gamma), _p(beta), eps, rows, h, float(p), int(seed), int(sid),
-           _p(y), _p(mean), _p(rstd), _st())
-    return y, mean, rstd
-
-
-def add_ln_rows_bwd(dy, x, res, row_map, gamma, mean, rstd, p, seed, sid):
-    rows, h = x.shape
-    dx, dres = empty((rows, h), BF16, x), empty((rows, h), BF16, x)
-    gb = torch.zeros((2,) + tuple(gamma.shape), dtype=gamma.dtype, device=gamma.device)
-    dgamma, dbeta = gb[0], gb[1]
-    L.call("mc_add_ln_rows_bwd", _p(dy), _p(x), _p(res), _p(row_map), _p(gamma), _p(mean), _p(rstd), rows, h, float(p),
-           int(seed), int(sid), _p(dx), _p(dres), _p(dgamma), _p(dbeta), _st())
-    return dx, dres, dgamma, dbeta
 
 
 def rows_gather(src, idx):

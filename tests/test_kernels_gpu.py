@@ -1173,6 +1173,30 @@ def test_fused_attention_vs_torch(b, t, nh):
         assert float(dqkv[dead][:, H:].float().abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("b,t,nh", [(2, 32, 1), (3, 64, 2)])
+def test_fused_attention_mask_with_holes(b, t, nh):
+    """the padded kernels take the key bias of an ARBITRARY mask, not a length: zeros at the start and in the middle of a
+    row (key 0 kept), one row all ones; one and two key blocks"""
+    H = nh * 64
+    qkv, dctx = rnd(b * t, 3 * H, seed=500 + t, scale=1.5), rnd(b * t, H, seed=501 + t)
+    mask = torch.ones(b, t, dtype=torch.long, device=DEV)
+    mask[0, 1:5] = 0                                   # start of the row
+    mask[0, t // 2 - 3:t // 2 + 6] = 0                 # middle (t = 64: across the key-block boundary)
+    if b > 2:                                          # row 1 stays all ones
+        mask[2, 2::3] = 0
+        mask[2, t - 7:] = 0
+    assert bool((mask[:, 0] == 1).all()) and bool((mask[1] == 1).all()) and not bool((mask[0] == 1).all())
+    maskb = ops.mask_bias(mask)
+    ctx, lse = ops.attn_fwd(qkv, maskb, b, t, nh, 0.125, 0.0, 1, 0)
+    ref, dref = _attn_torch(qkv, mask, dctx, b, t, nh)
+    check(ctx, ref, 1e-2, "attention context, mask with holes")
+    dqkv = ops.attn_bwd(qkv, maskb, dctx, lse, b, t, nh, 0.125, 0.0, 1, 0)
+    for i, nm in enumerate("QKV"):
+        check(dqkv[:, i * H:(i + 1) * H], dref[:, i * H:(i + 1) * H], 1.5e-2, "attention d%s, mask with holes" % nm)
+    dead = (mask == 0).view(-1)
+    assert float(dqkv[dead][:, H:].float().abs().max()) == 0.0          # masked keys: exactly zero dK / dV
+
+
 @pytest.mark.parametrize("b,t,nh", [(3, 256, 12), (4, 64, 2)])
 def test_fused_attention_dropout_matches_unfused_kernels(b, t, nh):
     """same (seed, stream, element) dropout function as mc_softmax_fwd: the fused kernels reproduce the unfused

@@ -178,12 +178,12 @@ def test_row_mapped_add_ln_and_embedding_are_bit_exact():
     dy, dyp, *_ = _padded_and_packed(lengths, T, h, 3)
     gamma, beta = rnd(h, seed=4, dtype=torch.float32) + 1.0, rnd(h, seed=5, dtype=torch.float32)
     y, mean, rstd = ops.add_ln_fwd(x, res, gamma, beta, 1e-12, p, seed, sid)
-    yp, meanp, rstdp = ops.add_ln_rows_fwd(xp, resp, pk.row_map, gamma, beta, 1e-12, p, seed, sid)
+    yp, meanp, rstdp = ops.add_ln_fwd(xp, resp, gamma, beta, 1e-12, p, seed, sid, row_map=pk.row_map)
     assert torch.equal(yp[:pk.real], y[real]) and torch.equal(meanp[:pk.real], mean[real]) and torch.equal(rstdp[:pk.real], rstd[real])
     assert torch.isfinite(yp.float()).all()
-    assert not torch.equal(yp[:pk.real], ops.add_ln_rows_fwd(xp, resp, pk.row_map, gamma, beta, 1e-12, 0.0, seed, sid)[0][:pk.real])
+    assert not torch.equal(yp[:pk.real], ops.add_ln_fwd(xp, resp, gamma, beta, 1e-12, 0.0, seed, sid, row_map=pk.row_map)[0][:pk.real])
     dx, dres, dg, db = ops.add_ln_bwd(dy, x, res, gamma, mean, rstd, p, seed, sid)
-    dxp, dresp, dgp, dbp = ops.add_ln_rows_bwd(dyp, xp, resp, pk.row_map, gamma, meanp, rstdp, p, seed, sid)
+    dxp, dresp, dgp, dbp = ops.add_ln_bwd(dyp, xp, resp, gamma, meanp, rstdp, p, seed, sid, row_map=pk.row_map)
     assert torch.equal(dxp[:pk.real], dx[real]) and torch.equal(dresp[:pk.real], dres[real])
     assert float(dxp[pk.real:].float().abs().sum()) == 0.0 and float(dresp[pk.real:].float().abs().sum()) == 0.0
     check(dgp, dg, 1e-4, "add_ln dgamma")       # fp32 sums of the same terms (zero rows aside) in another order
@@ -196,11 +196,11 @@ def test_row_mapped_add_ln_and_embedding_are_bit_exact():
     word, pos, typ = (rnd(n, h, seed=10 + i, dtype=torch.float32) for i, n in enumerate((V, 64, 2)))
     ids_p, tt_p = ids.view(-1)[pk.src.long()].contiguous(), tt.view(-1)[pk.src.long()].contiguous()
     e, em, er = ops.bert_embed_fwd(ids, tt, word, pos, typ, gamma, beta, 1e-12, p, seed, 15)
-    ep, epm, epr = ops.bert_embed_rows_fwd(ids_p, tt_p, pk, word, pos, typ, gamma, beta, 1e-12, p, seed, 15)
+    ep, epm, epr = ops.bert_embed_fwd(ids_p, tt_p, word, pos, typ, gamma, beta, 1e-12, p, seed, 15, pk=pk)
     assert torch.equal(ep[:pk.real], e[real]) and torch.equal(epm[:pk.real], em[real]) and torch.equal(epr[:pk.real], er[real])
     assert float(ep[pk.real:].float().abs().sum()) == 0.0
     ref = ops.bert_embed_bwd(dy, ids, tt, word, pos, typ, gamma, em, er, p, seed, 15)
-    got = ops.bert_embed_rows_bwd(dyp, ids_p, tt_p, pk, word, pos, typ, gamma, epm, epr, p, seed, 15)
+    got = ops.bert_embed_bwd(dyp, ids_p, tt_p, word, pos, typ, gamma, epm, epr, p, seed, 15, pk=pk)
     for nm, a, r in zip(("dword", "dpos", "dtype", "dgamma", "dbeta"), got, ref):
         check(a, r, 1e-4, "embedding " + nm)     # fp32 atomic sums of identical terms
 
