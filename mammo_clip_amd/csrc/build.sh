@@ -9,14 +9,13 @@
 set -e
 cd "$(dirname "$0")"
 if [ "${MC_REBUILD:-0}" = "1" ]; then rm -f ../lib/*.o ../lib/f16/*.o ../lib/libmammoclip_hip.so ../lib/libmammoclip_hip_f16.so; fi
-SRCS="gemm gemm256 gemm256_tn fp8 gemm_rows gemm_wgrad_rows conv conv_lane bnact bnfold bert attn head retrieval augment optim util"
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result"
+CSRC=. && . ./units.sh     # SRCS, FLAGS, unit_stale
 pids=()
 compile_variant() {   # $1 = object directory, $2 = extra flags
   local OUT=$1 EXTRA=$2
   mkdir -p $OUT
   for f in $SRCS; do
-    if [ ! -f $OUT/$f.o ] || [ $f.hip -nt $OUT/$f.o ] || [ common_hip.h -nt $OUT/$f.o ] || [ ../../include/mammoclip_hip.h -nt $OUT/$f.o ]; then
+    if unit_stale $OUT $f; then
       ( hipcc $FLAGS $EXTRA -c $f.hip -o $OUT/$f.o.tmp && mv $OUT/$f.o.tmp $OUT/$f.o ) &
       pids+=($!)
     fi

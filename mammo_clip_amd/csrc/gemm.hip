@@ -16,12 +16,23 @@
 // one barrier per K tile, register-staged tiles prefetched across K tiles AND across row blocks.
 // The bf16 epilogue goes back through LDS so global stores are 16-byte row segments, and can emit per-column
 // sum / sum-of-squares partials (training-mode BatchNorm statistics of the conv output).
-#include "common_hip.h"
+//
+// This file: the 128-row tile kernel in its two staging forms (register-staged: every layout and prologue; direct-to-LDS:
+// plain NT / TN operands), the split-K combine kernel of the WHOLE family, the argument checks and the routing to
+// gemm256.hip (256 x 256 plain NT) and gemm256_tn.hip (256 x 256 TN weight gradient).  What the three share -- the K range
+// of a split, the transpose fragment read, the LDS swizzles -- is in gemm_tile.h.
+#include "gemm_tile.h"
 #include <cstdlib>
-#include <type_traits>
-#include "../../include/mammoclip_hip.h"
+#include <utility>
 
 namespace {
+using namespace gt;
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>): a loop whose index is a compile-time constant in the body
+template <class F, int... I>
+__device__ __forceinline__ void for_each_index(std::integer_sequence<int, I...>, F&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
 
 __device__ __forceinline__ uint4 zero4() { return make_uint4(0u, 0u, 0u, 0u); }
 // component-wise (a select between two uint4 STRUCTS is lowered through scratch memory)
@@ -50,41 +61,25 @@ __device__ __forceinline__ uint4 apply_prologue(uint4 v, const mc_gemm_args& p, 
     return pack8(f);
 }
 
-// k-major operands (reduction index = row of the stored matrix) stay ROW-MAJOR in LDS ([k][x], 16-byte stores) and
-// are turned into MFMA fragments by gfx950's LDS transpose-read: within a 16-lane group lane i supplies the address
-// of row i/4, cols (i%4)*4..+3 of a 4x16 block and lane c receives column c, rows 0..3 (verified on hardware).
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((address_space(3))) s4_t lds_s4_t;
+// register-staged k-major operands (reduction index = row of the stored matrix) stay ROW-MAJOR in LDS ([k][x], 16-byte
+// stores, padded row stride rs) and are turned into MFMA fragments by the transpose-read (gemm_tile.h): fragment of k rows
+// row0 .. row0+31, columns col0 .. col0+15
 __device__ __forceinline__ bf16x8_t tr_frag(const unsigned char* tile, int rs, int row0, int col0, int lane) {
     const int g = lane >> 4, i = lane & 15;
     const unsigned char* a = tile + (size_t)(row0 + g * 8 + (i >> 2)) * rs + (col0 + (i & 3) * 4) * 2;
-    s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(a));
-    s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(a + 4 * rs));
-    typedef __attribute__((ext_vector_type(8))) short s8_t;
-    s8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8_t, v);
+    return tr_read(a, a + 4 * rs);
 }
 constexpr int tr_pad_bytes(int bx) { return bx >= 128 ? 48 : (bx >= 64 ? 16 : 32); }   // conflict-free tr-read strides
 
-#ifdef GEMM_PROF
-__device__ unsigned long long g_gemm_prof[8];      // developer phase profile (scripts/gemmbench.hip)
-#define GPROF(i) do { unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[i] += t_ - tprof; tprof = t_; } while (0)
-#else
-#define GPROF(i)
-#endif
-
 // GL = operands go global -> LDS directly (global_load_lds_dwordx4, no register staging, no ds_write pass).  The DMA
 // writes a wave-instruction's 64 x 16 B lane-linearly, so the LDS image is plain [row][8 x 16 B] (BK = 64) and the
-// bank-conflict swizzle is applied on the SOURCE side: the lane that fills slot s of row r fetches chunk
-// s ^ ((r >> 1) & 7) (still the same 128-byte line per row); ds_read_b128 of a fragment then spreads 16 rows x one
-// chunk over all 64 banks.  Chunks outside the matrices are fetched from a 16-byte zero block.  Plain NT only.
+// bank-conflict swizzle is applied on the SOURCE side (swz_kc / swz_km of gemm_tile.h).  Chunks outside the matrices are
+// fetched from a 16-byte zero block.  Plain NT, or both operands k-major.
 __device__ __attribute__((aligned(16))) unsigned int g_gemm_zero16[4];
-typedef __attribute__((address_space(3))) unsigned int lds_u32_t;
 typedef __attribute__((address_space(1))) const unsigned int glb_u32_t;
-// Issued as inline assembly: the compiler then keeps no book on the DMA, so the kernel's own counted s_waitcnt vmcnt(N)
-// decides when a stage is ready and the transfers of LATER stages stay in flight across barriers and LDS reads (with
-// the builtin every LDS access after a DMA waits for vmcnt(0)).  dst_wave_base must be wave-uniform; lane l's 16 bytes
-// land at dst_wave_base + 16 l.  M0 (the LDS destination) is saved and restored around the instruction.
+// Issued as inline assembly: the compiler then keeps no book on the DMA, so the kernel's own s_waitcnt decides when a
+// stage is ready (with the builtin every LDS access after a DMA waits for vmcnt(0)).  dst_wave_base must be wave-uniform;
+// lane l's 16 bytes land at dst_wave_base + 16 l.  M0 (the LDS destination) is saved and restored around the instruction.
 __device__ __forceinline__ void glds16(const void* src, unsigned dst_wave_base) {     // dst: LDS byte address
     const unsigned lds = __builtin_amdgcn_readfirstlane(dst_wave_base);
     unsigned keep;
@@ -93,12 +88,11 @@ __device__ __forceinline__ void glds16(const void* src, unsigned dst_wave_base) 
 }
 
 template <int BM, int BN, int BK, int WGM, int WGN, int LAY, int PRO, bool CF32, bool GL = false>
-__global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) void gemm_kernel(const mc_gemm_args p, const int gm) {
-    static_assert(!GL || ((LAY == 0 || LAY == 2) && PRO == 0 && BK == 64 && BM % 64 == 0 && BN % 64 == 0 &&
-                          (WGM * WGN == 4 || (WGM * WGN == 8 && LAY == 0))),
-                  "direct-to-LDS staging: plain operands (NT or both k-major), 64-wide K tiles, 4 waves (NT: or 8)");
-    // 8-wave tiles are held to <= 128 VGPRs so two workgroups (16 waves) fit a CU
-    constexpr int NT = WGM * WGN * 64;                // threads per workgroup (4 or 8 waves)
+__global__ __launch_bounds__(WGM * WGN * 64, 2) void gemm_kernel(const mc_gemm_args p, const int gm) {
+    static_assert(WGM * WGN == 4, "4 waves per workgroup");
+    static_assert(!GL || ((LAY == 0 || LAY == 2) && PRO == 0 && BK == 64 && BM % 64 == 0 && BN % 64 == 0),
+                  "direct-to-LDS staging: plain operands (NT or both k-major), 64-wide K tiles");
+    constexpr int NT = WGM * WGN * 64;                // threads per workgroup
     constexpr bool AKM = (LAY == 2), BKM = (LAY >= 1);
     constexpr int ROWB = BK * 2 + 16;                 // padded LDS row: conflict-light ds_read_b128
     constexpr int WM = BM / WGM, WN = BN / WGN;
@@ -114,13 +108,9 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
     // epilogue tile row bytes (bf16).  GL: the tile must fit the stage that was just consumed (the other one is being
     // filled), so rows are unpadded and the 16-byte chunk index is XOR-swizzled with the row instead
     constexpr int CROW = GL ? BN * 2 : (BN + 8) * 2;
-    constexpr int EH = (GL && !CF32 && BM * CROW > STAGE_BYTES) ? 2 : 1;      // epilogue passes (row halves of the tile)
-    constexpr int EROWS = BM / EH;
-    constexpr int EPI_BYTES = CF32 ? 0 : EROWS * CROW;
+    constexpr int EPI_BYTES = CF32 ? 0 : BM * CROW;
     static_assert(!GL || EPI_BYTES <= STAGE_BYTES, "epilogue tile must fit one stage");
-    // GL stages: as many as fit beside nothing else in 160 KB at one (8-wave) or two (4-wave) workgroups per CU
-    constexpr int NS = GL ? ((WGM * WGN == 8) ? 3 : 2) : 2;
-    constexpr int LDS_BYTES = (NS * STAGE_BYTES > EPI_BYTES) ? NS * STAGE_BYTES : EPI_BYTES;
+    constexpr int LDS_BYTES = (2 * STAGE_BYTES > EPI_BYTES) ? 2 * STAGE_BYTES : EPI_BYTES;      // two stages
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -159,21 +149,8 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
     const long long coff = b1 * p.sC1 + b2 * p.sC2;
     const float* bias = p.bias ? p.bias + (long long)b1 * p.bias_stride1 : nullptr;
 
-    // K range of this split (multiples of BK)
-    const long long ktiles = (p.K + BK - 1) / BK;
-    const long long tps = (ktiles + p.splits - 1) / p.splits;
-    long long kbeg = (long long)split * tps * BK;
-    long long kend = kbeg + tps * BK;
-    if (p.split_group_rows > 0) {
-        // grouped split-K: the reduction index is cut at group (= image) boundaries, split_sub splits per group, so
-        // that a per-(group, column) factor can be applied when the partials are combined (see splitk_reduce_kernel)
-        const long long grp = split / p.split_sub, j = split % p.split_sub;
-        const long long chunk = (p.split_group_rows + p.split_sub - 1) / p.split_sub;
-        kbeg = grp * p.split_group_rows + j * chunk;
-        kend = kbeg + chunk;
-        if (kend > (grp + 1) * p.split_group_rows) kend = (grp + 1) * p.split_group_rows;
-    }
-    if (kend > p.K) kend = p.K;
+    const KRange ks = split_k_range(p, split, BK);                 // K range of this split
+    const long long kbeg = ks.kbeg, kend = ks.kend;
     const long long mtiles = (p.M + BM - 1) / BM;
     const bool n_full = n0 + BN <= p.N;
 
@@ -256,64 +233,53 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
         // is not always unrolled, and a runtime index would push the register stage into scratch)
         auto store_a = [&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
-            if constexpr (i < A_REGS) {
-                const int c = tid + i * NT;
-                if (c < (AKM ? BK * (BM / 8) : BM * KCH)) {
-                    uint4 v = keep4(full || a_valid(i, m0, k0), ra[i]);
-                    if (!AKM) {
-                        const int row = c / KCH, kc = c % KCH;
-                        if (PRO == 1) {
-                            const long long m = m0 + row, k = k0 + kc * 8;
-                            if (m < p.M && k < kend) v = apply_prologue(v, p, m, (int)k);
-                        }
-                        *reinterpret_cast<uint4*>(sA + row * ROWB + kc * 16) = v;
-                    } else {
-                        const int xc = c % (BM / 8), kr = c / (BM / 8);
-                        *reinterpret_cast<uint4*>(sA + kr * RSA + xc * 16) = v;
+            const int c = tid + i * NT;
+            if (c < (AKM ? BK * (BM / 8) : BM * KCH)) {
+                uint4 v = keep4(full || a_valid(i, m0, k0), ra[i]);
+                if (!AKM) {
+                    const int row = c / KCH, kc = c % KCH;
+                    if (PRO == 1) {
+                        const long long m = m0 + row, k = k0 + kc * 8;
+                        if (m < p.M && k < kend) v = apply_prologue(v, p, m, (int)k);
                     }
+                    *reinterpret_cast<uint4*>(sA + row * ROWB + kc * 16) = v;
+                } else {
+                    const int xc = c % (BM / 8), kr = c / (BM / 8);
+                    *reinterpret_cast<uint4*>(sA + kr * RSA + xc * 16) = v;
                 }
             }
         };
         auto store_b = [&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
-            if constexpr (i < B_REGS) {
-                const int c = tid + i * NT;
-                if (c < (BKM ? BK * (BN / 8) : BN * KCH)) {
-                    uint4 v = keep4(full || b_valid(i, k0), rb[i]);
-                    if (!BKM) {
-                        const int row = c / KCH, kc = c % KCH;
-                        if (PRO == 3) {          // batch = image: the SE gate of this image scales the weight columns
-                            const long long k = k0 + kc * 8;
-                            if (k < kend) {
-                                float f[8], g[8];
-                                unpack8(v, f);
-                                load8f(p.pro_gate + (long long)b1 * p.pro_nch + k, g);
+            const int c = tid + i * NT;
+            if (c < (BKM ? BK * (BN / 8) : BN * KCH)) {
+                uint4 v = keep4(full || b_valid(i, k0), rb[i]);
+                if (!BKM) {
+                    const int row = c / KCH, kc = c % KCH;
+                    if (PRO == 3) {          // batch = image: the SE gate of this image scales the weight columns
+                        const long long k = k0 + kc * 8;
+                        if (k < kend) {
+                            float f[8], g[8];
+                            unpack8(v, f);
+                            load8f(p.pro_gate + (long long)b1 * p.pro_nch + k, g);
 #pragma unroll
-                                for (int q = 0; q < 8; ++q) f[q] *= g[q];
-                                v = pack8(f);
-                            }
+                            for (int q = 0; q < 8; ++q) f[q] *= g[q];
+                            v = pack8(f);
                         }
-                        *reinterpret_cast<uint4*>(sB + row * ROWB + kc * 16) = v;
-                    } else {
-                        const int xc = c % (BN / 8), kr = c / (BN / 8);
-                        if (PRO == 2) {
-                            const long long n = n0 + xc * 8, k = k0 + kr;
-                            if (n < p.N && k < kend) v = apply_prologue(v, p, k, (int)n);
-                        }
-                        *reinterpret_cast<uint4*>(sB + kr * RSB + xc * 16) = v;
                     }
+                    *reinterpret_cast<uint4*>(sB + row * ROWB + kc * 16) = v;
+                } else {
+                    const int xc = c % (BN / 8), kr = c / (BN / 8);
+                    if (PRO == 2) {
+                        const long long n = n0 + xc * 8, k = k0 + kr;
+                        if (n < p.N && k < kend) v = apply_prologue(v, p, k, (int)n);
+                    }
+                    *reinterpret_cast<uint4*>(sB + kr * RSB + xc * 16) = v;
                 }
             }
         };
-        static_assert(A_REGS <= 8 && B_REGS <= 8, "chunk lists below cover 8 per operand");
-        store_a(std::integral_constant<int, 0>{}); store_a(std::integral_constant<int, 1>{});
-        store_a(std::integral_constant<int, 2>{}); store_a(std::integral_constant<int, 3>{});
-        store_a(std::integral_constant<int, 4>{}); store_a(std::integral_constant<int, 5>{});
-        store_a(std::integral_constant<int, 6>{}); store_a(std::integral_constant<int, 7>{});
-        store_b(std::integral_constant<int, 0>{}); store_b(std::integral_constant<int, 1>{});
-        store_b(std::integral_constant<int, 2>{}); store_b(std::integral_constant<int, 3>{});
-        store_b(std::integral_constant<int, 4>{}); store_b(std::integral_constant<int, 5>{});
-        store_b(std::integral_constant<int, 6>{}); store_b(std::integral_constant<int, 7>{});
+        for_each_index(std::make_integer_sequence<int, A_REGS>{}, store_a);
+        for_each_index(std::make_integer_sequence<int, B_REGS>{}, store_b);
     };
 
     f32x4_t acc[FM][FN];
@@ -386,67 +352,79 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
             const int cc = tid % CPR, r0 = tid / CPR;
             const int n = n0 + cc * 8;
 #pragma unroll
-            for (int eh = 0; eh < EH; ++eh) {          // the tile goes out in EH row slabs of EROWS rows
-                if (eh > 0) __syncthreads();
-                if (EH == 1 || (wm * WM) / EROWS == eh) {
+            for (int j = 0; j < FN; ++j) {
+                int nn = n0 + ncol + j * 16;
+                float bv[4] = {0.f, 0.f, 0.f, 0.f};
+                if (bias) {
 #pragma unroll
-                    for (int j = 0; j < FN; ++j) {
-                        int nn = n0 + ncol + j * 16;
-                        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-                        if (bias) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) bv[r] = (nn + r < p.N) ? bias[nn + r] : 0.f;
-                        }
-#pragma unroll
-                        for (int i = 0; i < FM; ++i) {
-                            uint2 pk = make_uint2(pack_bf2(acc[i][j][0] * alpha + bv[0], acc[i][j][1] * alpha + bv[1]),
-                                                  pack_bf2(acc[i][j][2] * alpha + bv[2], acc[i][j][3] * alpha + bv[3]));
-                            *reinterpret_cast<uint2*>(etile + eoff(mrow + i * 16 - eh * EROWS, (ncol + j * 16) >> 3, ((ncol + j * 16) & 7) * 2)) = pk;
-                        }
-                    }
+                    for (int r = 0; r < 4; ++r) bv[r] = (nn + r < p.N) ? bias[nn + r] : 0.f;
                 }
-                __syncthreads();
-                if (n < p.N) {
-                    for (int row = r0; row < EROWS; row += RPP) {
-                        long long m = m0 + eh * EROWS + row;
-                        if (m >= p.M) break;
-                        uint4 v = *reinterpret_cast<const uint4*>(etile + eoff(row, cc, 0));
-                        if (p.R) {
-                            float f[8], g[8];
-                            unpack8(v, f);
-                            uint4 rv = *reinterpret_cast<const uint4*>(p.R + coff + m * p.ldr + n);
-                            unpack8(rv, g);
 #pragma unroll
-                            for (int q = 0; q < 8; ++q) f[q] += g[q];
-                            v = pack8(f);
-                        }
-                        if (p.stat_partials) {
-                            float f[8];
-                            unpack8(v, f);
+                for (int i = 0; i < FM; ++i) {
+                    uint2 pk = make_uint2(pack_bf2(acc[i][j][0] * alpha + bv[0], acc[i][j][1] * alpha + bv[1]),
+                                          pack_bf2(acc[i][j][2] * alpha + bv[2], acc[i][j][3] * alpha + bv[3]));
+                    *reinterpret_cast<uint2*>(etile + eoff(mrow + i * 16, (ncol + j * 16) >> 3, ((ncol + j * 16) & 7) * 2)) = pk;
+                }
+            }
+            __syncthreads();
+            if (n < p.N) {
+                for (int row = r0; row < BM; row += RPP) {
+                    long long m = m0 + row;
+                    if (m >= p.M) break;
+                    uint4 v = *reinterpret_cast<const uint4*>(etile + eoff(row, cc, 0));
+                    if (p.R) {
+                        float f[8], g[8];
+                        unpack8(v, f);
+                        uint4 rv = *reinterpret_cast<const uint4*>(p.R + coff + m * p.ldr + n);
+                        unpack8(rv, g);
 #pragma unroll
-                            for (int q = 0; q < 8; ++q) { colsum[q] += f[q]; colsq[q] += f[q] * f[q]; }
-                        }
-                        *reinterpret_cast<uint4*>(C + m * p.ldc + n) = v;
+                        for (int q = 0; q < 8; ++q) f[q] += g[q];
+                        v = pack8(f);
                     }
+                    if (p.stat_partials) {
+                        float f[8];
+                        unpack8(v, f);
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) { colsum[q] += f[q]; colsq[q] += f[q] * f[q]; }
+                    }
+                    *reinterpret_cast<uint4*>(C + m * p.ldc + n) = v;
                 }
             }
             __syncthreads();
         }
     };
 
-    // ---------------- direct-to-LDS main loop (GL) ----------------
-    // Per flat step: wait for this tile's DMA (the only one in flight), barrier (every wave's part has landed and every
-    // wave is done with the other stage), read ALL fragments of the tile into registers, issue the next tile's DMA into
-    // the other stage, then run the 2 x FM x FN MFMAs from registers while it lands.  No LDS read is ever issued while
-    // a DMA into LDS is outstanding, so the waits the compiler places for LDS-DMA coincide with the explicit one.
+    // ---------------- the flat tile stream ----------------
+    // The (row block, K tile) pairs this workgroup owns form one flat sequence of `total` steps; both main loops fetch
+    // ahead of the step they consume, across K tiles AND across row blocks.
+    const long long ktn = kbeg < kend ? (kend - kbeg + BK - 1) / BK : 0;
+    const long long my_mt = by < mtiles ? (mtiles - by + gm - 1) / gm : 0;
+    const long long total = my_mt * ktn;
+    if (ktn == 0) {
+        // an empty split still owes its (zero) partial tiles
+        for (long long mt = by; mt < mtiles; mt += gm) {
+            GT_CLEAR_ACC(acc);
+            epilogue(mt * BM);
+        }
+    } else {
+    // (m0, k0) of the next tile to fetch and of the tile being consumed, advanced incrementally (no divisions in the loops)
+    long long pm0 = (long long)by * BM, pk0 = kbeg;                      // position of the NEXT tile to fetch
+    auto advance = [&]() __attribute__((always_inline)) {
+        pk0 += BK;
+        if (pk0 >= kend) { pk0 = kbeg; pm0 += (long long)gm * BM; }
+    };
+    long long cm0 = pm0, ck0 = pk0;                                      // position of the tile being consumed
     if constexpr (GL) {
+        // ---------------- direct-to-LDS main loop ----------------
+        // Per flat step: wait for this tile's DMA (the only one in flight), barrier (every wave's part has landed and every
+        // wave is done with the other stage), read ALL fragments of the tile into registers, issue the next tile's DMA into
+        // the other stage, then run the 2 x FM x FN MFMAs from registers while it lands.  No LDS read is ever issued while
+        // a DMA into LDS is outstanding, so the waits the compiler places for LDS-DMA coincide with the explicit one.
         constexpr int NW = WGM * WGN;
         constexpr int NI_A = BM / (8 * NW), NI_B = BN / (8 * NW);   // wave-instructions (1 KiB each) per thread and operand
-        constexpr int NL = NI_A + NI_B;                        // DMA instructions per thread and tile
         // k-contiguous operand ([x][64 k], 128-byte rows, 8 rows per wave-instruction): slot s of row r holds chunk
-        //   s ^ ((r >> 1) & 7).  k-major operand ([64 k][x], 256-byte rows for x = 128, 4 rows per wave-instruction):
-        //   slot s of k-row r holds chunk s ^ (((r & 3) | ((r >> 1) & 4)) << 1), which keeps the 32-byte pairs the
-        //   transpose-read fetches together and spreads its 8 rows per 32-lane group over all banks.
+        //   s ^ swz_kc(r).  k-major operand ([64 k][x], 256-byte rows for x = 128, 4 rows per wave-instruction): slot s of
+        //   k-row r holds chunk s ^ 2 swz_km(r).
         // gx = offset along the operand's own rows (m or n), gk = offset along the reduction, in elements
         unsigned goffA[NI_A], goffB[NI_B];
         int gxA[NI_A], gxB[NI_B], gkA[NI_A], gkB[NI_B];
@@ -454,12 +432,12 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
         for (int i = 0; i < NI_A; ++i) {
             if (!AKM) {
                 const int row = (i * NW + wave) * 8 + (lane >> 3);
-                const int ch = (lane & 7) ^ ((row >> 1) & 7);
+                const int ch = (lane & 7) ^ swz_kc(row);
                 gxA[i] = row; gkA[i] = ch * 8; goffA[i] = (unsigned)(row * p.lda + ch * 8);
             } else {
                 static_assert(!AKM || BM == 128, "k-major direct staging is laid out for 128-wide tiles");
                 const int row = (i * NW + wave) * 4 + (lane >> 4);
-                const int ch = (lane & 15) ^ (((row & 3) | ((row >> 1) & 4)) << 1);
+                const int ch = (lane & 15) ^ (2 * swz_km(row));
                 gxA[i] = ch * 8; gkA[i] = row; goffA[i] = (unsigned)(row * p.lda + ch * 8);
             }
         }
@@ -467,12 +445,12 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
         for (int i = 0; i < NI_B; ++i) {
             if (!BKM) {
                 const int row = (i * NW + wave) * 8 + (lane >> 3);
-                const int ch = (lane & 7) ^ ((row >> 1) & 7);
+                const int ch = (lane & 7) ^ swz_kc(row);
                 gxB[i] = row; gkB[i] = ch * 8; goffB[i] = (unsigned)(row * p.ldb + ch * 8);
             } else {
                 static_assert(!BKM || BN == 128, "k-major direct staging is laid out for 128-wide tiles");
                 const int row = (i * NW + wave) * 4 + (lane >> 4);
-                const int ch = (lane & 15) ^ (((row & 3) | ((row >> 1) & 4)) << 1);
+                const int ch = (lane & 15) ^ (2 * swz_km(row));
                 gxB[i] = ch * 8; gkB[i] = row; goffB[i] = (unsigned)(row * p.ldb + ch * 8);
             }
         }
@@ -481,7 +459,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
         auto issue = [&](int stage, long long m0, long long k0) __attribute__((always_inline)) {
             const unsigned sA = smem_lds + stage * STAGE_BYTES;       // LDS byte addresses
             const unsigned sB = sA + A_BYTES;
-            if (n_full && (m0 + BM <= p.M) && (k0 + BK <= kend)) {
+            if (tile_full(m0, k0)) {
                 const bf16_t* ab = AKM ? A + k0 * p.lda + m0 : A + m0 * p.lda + k0;
                 const bf16_t* bb = BKM ? B + k0 * p.ldb + n0 : B + (long long)n0 * p.ldb + k0;
 #pragma unroll
@@ -501,70 +479,28 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
                 }
             }
         };
-        const long long ktn = kbeg < kend ? (kend - kbeg + BK - 1) / BK : 0;
-        const long long my_mt = by < mtiles ? (mtiles - by + gm - 1) / gm : 0;
-        const long long total = my_mt * ktn;
-        if (ktn == 0) {
-            for (long long mt = by; mt < mtiles; mt += gm) {
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-                epilogue(mt * BM);
-            }
-        } else {
-        long long pm0 = (long long)by * BM, pk0 = kbeg;                  // position of the NEXT tile to fetch
-        auto advance = [&]() __attribute__((always_inline)) {
-            pk0 += BK;
-            if (pk0 >= kend) { pk0 = kbeg; pm0 += (long long)gm * BM; }
-        };
-        long long cm0 = pm0, ck0 = pk0;                                  // position of the tile being consumed
-        constexpr int D = NS - 1;                                        // tiles in flight ahead of the one consumed
-        static_assert((D - 1) * NL < 16, "counted vmcnt wait is encoded in the low 4 bits");
-#pragma unroll
-        for (int t = 0; t < D; ++t)
-            if (t < total) { issue(t, pm0, pk0); advance(); }
-        // fragment addresses.  k-contiguous: row r, chunk c -> r * 128 + ((c ^ ((r >> 1) & 7)) << 4); the rows of a
-        // fragment are (lane & 15) + multiples of 16, so the swizzle term depends on the lane only.
-        // k-major (transpose-read, see tr_frag): lane (g, i) addresses k-row kk*32 + g*8 + (i >> 2) [+4 for the upper
+        // fragment addresses.  k-contiguous: row r, chunk c -> r * 128 + ((c ^ swz_kc(r)) << 4); the rows of a fragment
+        // are (lane & 15) + multiples of 16, so the swizzle term depends on the lane only.
+        // k-major (transpose-read, see tr_read): lane (g, i) addresses k-row kk*32 + g*8 + (i >> 2) [+4 for the upper
         // half], columns col0 + (i & 3) * 4 .. +3 -> 8 bytes inside chunk (col0 >> 3) + ((i & 3) >> 1).
-        const int frow = lane & 15, fsw = (frow >> 1) & 7, fkg = lane >> 4;
+        const int frow = lane & 15, fsw = swz_kc(frow), fkg = lane >> 4;
         const int ti = lane & 15, tg = lane >> 4;
         auto kc_off = [&](int x0, int kk) __attribute__((always_inline)) {      // k-contiguous operand, tile row base x0
             return (x0 + frow) * 128 + (((kk * 4 + fkg) ^ fsw) << 4);
         };
         auto km_off = [&](int col0, int kk, int hi) __attribute__((always_inline)) {   // k-major operand, 256-byte rows
             const int r = kk * 32 + tg * 8 + (ti >> 2) + hi * 4;
-            const int sw = ((r & 3) | ((r >> 1) & 4)) << 1;
-            return r * 256 + ((((col0 >> 3) + ((ti & 3) >> 1)) ^ sw) << 4) + ((ti & 1) << 3);
+            return r * 256 + ((((col0 >> 3) + ((ti & 3) >> 1)) ^ (2 * swz_km(r))) << 4) + ((ti & 1) << 3);
         };
-        typedef __attribute__((ext_vector_type(8))) short s8_t;
         auto km_frag = [&](const unsigned char* tile, int col0, int kk) __attribute__((always_inline)) {
-            s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(tile + km_off(col0, kk, 0)));
-            s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(tile + km_off(col0, kk, 1)));
-            s8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            return __builtin_bit_cast(bf16x8_t, v);
+            return tr_read(tile + km_off(col0, kk, 0), tile + km_off(col0, kk, 1));
         };
-#ifdef GEMM_PROF
-        unsigned long long pacc[6] = {0, 0, 0, 0, 0, 0};
-        unsigned long long tprof = __builtin_amdgcn_s_memtime();
-#endif
-        int buf = 0, nbuf = D % NS;             // stage being consumed / stage the next issue goes to
-        bool drain = false;                     // stores of an epilogue are in the queue: count nothing, wait for all
+        if (0 < total) { issue(0, pm0, pk0); advance(); }
+        int buf = 0;                            // stage being consumed; the next tile goes to the other one
         for (long long i = 0; i < total; ++i) {
-            if (ck0 == kbeg) {
-#pragma unroll
-                for (int a = 0; a < FM; ++a)
-#pragma unroll
-                    for (int b = 0; b < FN; ++b) acc[a][b] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            }
-            // tile i has landed once at most the D-1 tiles issued after it are still outstanding (loads return in order)
-            if (D > 1 && !drain && i + D - 1 < total) __builtin_amdgcn_s_waitcnt(0x0F70 | ((D - 1) * NL));
-            else __builtin_amdgcn_s_waitcnt(0x0F70);
-            drain = false;
-            GPROF(0);
-            __builtin_amdgcn_s_barrier();       // every wave's part of tile i is in LDS; everyone is done with stage nbuf
-            GPROF(1);
+            if (ck0 == kbeg) GT_CLEAR_ACC(acc);                 // first K tile of an output tile
+            __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0): tile i, the only one in flight, has landed
+            __builtin_amdgcn_s_barrier();       // every wave's part of tile i is in LDS; everyone is done with the other stage
             const unsigned char* sA = smem + buf * STAGE_BYTES;
             const unsigned char* sB = sA + A_BYTES;
             bf16x8_t af[2][FM], bfr[2][FN];
@@ -581,11 +517,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
                     else bfr[kk][b] = *reinterpret_cast<const bf16x8_t*>(sB + kc_off(wn * WN + b * 16, kk));
                 }
             }
-#ifdef GL_WAIT_FRAGS
-            __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): fragments are in registers
-#endif
-            if (i + D < total) { issue(nbuf, pm0, pk0); advance(); }
-            GPROF(2);
+            if (i + 1 < total) { issue(buf ^ 1, pm0, pk0); advance(); }
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -593,86 +525,36 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
 #pragma unroll
                     for (int b = 0; b < FN; ++b)
                         acc[a][b] = MC_MFMA_16x16x32(bfr[kk][b], af[kk][a], acc[a][b], 0, 0, 0);
-            GPROF(3);
             const bool last_k = ck0 + BK >= kend;
-            if (last_k) { ebuf = buf; epilogue(cm0); drain = true; }
-            buf = buf + 1 == NS ? 0 : buf + 1;
-            nbuf = nbuf + 1 == NS ? 0 : nbuf + 1;
-            GPROF(4);
-#ifdef GEMM_PROF
-            pacc[5] += 1;
-#endif
+            if (last_k) { ebuf = buf; epilogue(cm0); }
+            buf ^= 1;
             ck0 += BK;
             if (last_k) { ck0 = kbeg; cm0 += (long long)gm * BM; }
         }
-#ifdef GEMM_PROF
-        if (tid == 0)
-            for (int q = 0; q < 6; ++q) atomicAdd(&g_gemm_prof[q], pacc[q]);
-#endif
-        }
-    }
-
-    // ---------------- software-pipelined main loop ----------------
-    if constexpr (!GL) {
-    // The (row block, K tile) pairs this workgroup owns form one flat sequence; two tiles are always in flight in
-    // registers (global loads are issued two steps ahead of the LDS store that consumes them), across K tiles AND
-    // across row blocks, so HBM/L2 latency is covered even when a row block has only one or two K tiles.
-    const long long ktn = kbeg < kend ? (kend - kbeg + BK - 1) / BK : 0;
-    const long long my_mt = by < mtiles ? (mtiles - by + gm - 1) / gm : 0;
-    const long long total = my_mt * ktn;
-    if (ktn == 0) {
-        for (long long mt = by; mt < mtiles; mt += gm) {
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            epilogue(mt * BM);
-        }
     } else {
-        // (m0, k0) of flat step i, advanced incrementally (no divisions in the loop)
-        long long pm0 = (long long)by * BM, pk0 = kbeg;                  // position of the NEXT tile to load
-        auto advance = [&]() __attribute__((always_inline)) {
-            pk0 += BK;
-            if (pk0 >= kend) { pk0 = kbeg; pm0 += (long long)gm * BM; }
-        };
-        long long cm0 = pm0, ck0 = pk0;                                  // position of the tile being consumed
+        // ---------------- register-staged, software-pipelined main loop ----------------
+        // Two tiles are always in flight in registers (global loads are issued two steps ahead of the LDS store that
+        // consumes them), so HBM/L2 latency is covered even when a row block has only one or two K tiles.
         if (0 < total) { load_tiles(ra0, rb0, pm0, pk0); advance(); }
         if (1 < total) { load_tiles(ra1, rb1, pm0, pk0); advance(); }
         int buf = 0;
-#ifdef GEMM_PROF
-        unsigned long long pacc[6] = {0, 0, 0, 0, 0, 0};
-        unsigned long long tprof = __builtin_amdgcn_s_memtime();
-#endif
         // one flat step; the loop below is unrolled by two so that each register stage is named statically (a runtime
         // stage selector makes the compiler rotate the stages with register copies, which forces it to wait for the
         // loads that are still in flight)
         auto step = [&](uint4 (&ra)[A_REGS], uint4 (&rb)[B_REGS], long long i) __attribute__((always_inline)) {
-            if (ck0 == kbeg) {
-#pragma unroll
-                for (int a = 0; a < FM; ++a)
-#pragma unroll
-                    for (int b = 0; b < FN; ++b) acc[a][b] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            }
+            if (ck0 == kbeg) GT_CLEAR_ACC(acc);                 // first K tile of an output tile
             store_tiles(ra, rb, buf, cm0, ck0);
-            GPROF(0);
             __syncthreads();
-            GPROF(1);
             {   // unconditional (the last two steps re-load their own tile, never consumed): with exactly one tile of
                 // loads per step on every path the compiler can count them, and waits vmcnt(N) instead of vmcnt(0)
                 const bool more = i + 2 < total;
                 load_tiles(ra, rb, more ? pm0 : cm0, more ? pk0 : ck0);
                 if (more) advance();
             }
-            GPROF(2);
             compute(buf);
-            GPROF(3);
             buf ^= 1;
             const bool last_k = ck0 + BK >= kend;
             if (last_k) epilogue(cm0);
-            GPROF(4);
-#ifdef GEMM_PROF
-            pacc[5] += 1;
-#endif
             ck0 += BK;
             if (last_k) { ck0 = kbeg; cm0 += (long long)gm * BM; }
         };
@@ -680,13 +562,9 @@ __global__ __launch_bounds__(WGM * WGN * 64, (WGM * WGN == 8 && !GL) ? 4 : 2) vo
             step(ra0, rb0, i);
             if (i + 1 < total) step(ra1, rb1, i + 1);
         }
-#ifdef GEMM_PROF
-        if (tid == 0)
-            for (int q = 0; q < 6; ++q) atomicAdd(&g_gemm_prof[q], pacc[q]);
-#endif
     }
+    }   // ktn > 0
 
-    }   // !GL
     // ---------------- column statistics partials ----------------
     if (!CF32 && p.stat_partials) {
         constexpr int CPR = BN / 8;
@@ -758,26 +636,28 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, l
     }
 }
 
+// combines the split-K workspace of any tile kernel of the family into C
+int launch_splitk_reduce(const mc_gemm_args& p, hipStream_t st) {
+    const long long mn = p.M * p.N;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(mc_div_up(mc_div_up(mn, 4), 256)), dim3(256), 0, st, p.splitk_ws,
+                       p.splits, mn, p.N, reinterpret_cast<float*>(p.C), p.ldc, p.c_atomic, p.split_scale,
+                       p.split_sub > 0 ? p.split_sub : 1);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
 template <int BM, int BN, int BK, int WGM, int WGN, int LAY, int PRO, bool CF32, bool GL = false>
 int launch(const mc_gemm_args& p, int grid_m, hipStream_t st) {
-    constexpr int NT = WGM * WGN * 64;
     dim3 grid(mc_div_up(p.N, BN), grid_m >= 16 ? (grid_m + 7) / 8 * 8 : grid_m, p.batch * p.splits);   // see the XCD remap
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, WGM, WGN, LAY, PRO, CF32, GL>), grid, dim3(NT), 0, st, p, grid_m);
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, WGM, WGN, LAY, PRO, CF32, GL>), grid, dim3(WGM * WGN * 64), 0, st, p, grid_m);
     MC_LAUNCH_CHECK();
-    if (p.splits > 1 && p.splitk_ws) {
-        long long mn = p.M * p.N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(mc_div_up(mc_div_up(mn, 4), NT)), dim3(NT), 0, st, p.splitk_ws,
-                           p.splits, mn, p.N, reinterpret_cast<float*>(p.C), p.ldc, p.c_atomic, p.split_scale,
-                           p.split_sub > 0 ? p.split_sub : 1);
-        MC_LAUNCH_CHECK();
-    }
+    if (p.splits > 1 && p.splitk_ws) return launch_splitk_reduce(p, st);
     return MC_OK;
 }
 
 static int mc_gemm_glds_enabled() {
     static int on = -1;
-    // developer A/B switch: 0 = register staging, 1 = direct-to-LDS 128x128 tiles (default), 2 = also 256x128 tiles
-    // (8 waves, 3 stages; measured 0.9-1.07x of the 128x128 configuration on the model's shapes -- not the default)
+    // developer A/B switch: 0 = register staging, anything else = direct-to-LDS 128x128 tiles (default)
     if (on < 0) { const char* e = getenv("MC_GEMM_GLDS"); on = e ? atoi(e) : 1; }
     return on;
 }
@@ -785,19 +665,10 @@ static int mc_gemm_glds_enabled() {
 template <int LAY, int PRO, bool CF32>
 int dispatch_tile(const mc_gemm_args& p, int grid_m, hipStream_t st) {
     const bool small_k = p.K <= 48;
-    // 128x128 tiles run with 8 waves (wave tile 64x32): half the accumulator / staging registers per thread,
-    // twice the waves per CU to overlap global->LDS staging with MFMA issue
     if (p.N > 64) {
         if constexpr ((LAY == 0 || LAY == 2) && PRO == 0) {
             // plain operands: direct-to-LDS staging
-            if (!small_k && mc_gemm_glds_enabled()) {
-                if constexpr (LAY == 0) {
-                    // 256 x 128 tiles (8 waves, 3 stages, one workgroup per CU) once there are >= 2 tiles per CU
-                    const long long t256 = ((p.M + 255) / 256) * mc_div_up(p.N, 128) * p.batch * p.splits;
-                    if (t256 >= 512 && mc_gemm_glds_enabled() == 2) return launch<256, 128, 64, 4, 2, LAY, PRO, CF32, true>(p, grid_m, st);
-                }
-                return launch<128, 128, 64, 2, 2, LAY, PRO, CF32, true>(p, grid_m, st);
-            }
+            if (!small_k && mc_gemm_glds_enabled()) return launch<128, 128, 64, 2, 2, LAY, PRO, CF32, true>(p, grid_m, st);
         }
         return small_k ? launch<128, 128, 32, 2, 2, LAY, PRO, CF32>(p, grid_m, st)
                        : launch<128, 128, 64, 2, 2, LAY, PRO, CF32>(p, grid_m, st);
@@ -882,12 +753,7 @@ extern "C" int mc_gemm_bf16(const mc_gemm_args* a, void* stream) {
     if (mc_gemm256_tn_eligible(&p)) {
         const int rc = mc_gemm256_tn_launch(&p, stream);
         if (rc != MC_OK || p.splits <= 1) return rc;
-        const long long mn = p.M * p.N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(mc_div_up(mc_div_up(mn, 4), 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                           p.splitk_ws, p.splits, mn, p.N, reinterpret_cast<float*>(p.C), p.ldc, p.c_atomic, p.split_scale,
-                           p.split_sub > 0 ? p.split_sub : 1);
-        MC_LAUNCH_CHECK();
-        return MC_OK;
+        return launch_splitk_reduce(p, reinterpret_cast<hipStream_t>(stream));
     }
     MC_CHECK(!p.ab_fp8 && !p.alpha_dev, "gemm: fp8 operands / alpha_dev need the plain NT bf16-output form (gemm256)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -9,7 +9,7 @@
 //     x 2 stage buffers (+ a 32 KB epilogue slab); half h of A holds, for BOTH wave rows, the 64 rows of C-quadrant row h,
 //     half h of B the 32 columns of quadrant column h of all four wave columns
 //   * LDS-direct DMA; it writes lane-linearly, so the bank-conflict swizzle sits on the SOURCE address: slot s of LDS row r
-//     holds 16-byte chunk s ^ ((r >> 1) & 7) of that row's 128 bytes (conflict-free for ds_read_b128's 16-lane groups)
+//     holds 16-byte chunk s ^ swz_kc(r) of that row's 128 bytes (gemm_tile.h)
 //   * 4 phases per K tile, one C quadrant (16 MFMAs per wave) and ONE half-tile DMA issue (2 instructions per wave) per
 //     phase; the DMA stream runs 3 half-tiles ahead behind a counted s_waitcnt vmcnt(6) once per K tile -- it never drains
 //     in the main loop -- and crosses output-tile boundaries (persistent workgroups, one flat K-tile stream):
@@ -35,10 +35,12 @@
 //   * work order: the 32 workgroups of an XCD walk the tile grid in panels of 4 row blocks x all column tiles, column-major
 //     inside a panel, so the tiles in flight on one L2 form a ~4 x 8 block (12 operand panels per K step instead of 33 for
 //     a 1 x 32 strip: the 8192^3 case was HBM/MALL-bound on re-fetched B panels)
-#include "common_hip.h"
-#include "../../include/mammoclip_hip.h"
+// The DMA, barrier, swizzle and bf16 MFMA-quadrant helpers are shared with gemm256_tn.hip through gemm_tile.h; this file
+// keeps the NT staging geometry, the 4-phase loop, the fp8 quadrant, the bf16 epilogue and the host-side routing rule.
+#include "gemm_tile.h"
 
 namespace g8 {
+using namespace gt;
 
 constexpr int BM = 256, BN = 256, NTHR = 512;
 constexpr int HALF_BYTES = 128 * 128;            // 128 LDS rows of 128 bytes
@@ -47,24 +49,6 @@ constexpr int EPI_OFF = 2 * STAGE_BYTES;         // 128 KB
 constexpr int EPI_BYTES = 64 * BN * 2;           // one slab: 64 rows x 256 columns bf16 = 32 KB
 constexpr int LDS_BYTES = EPI_OFF + EPI_BYTES;   // 160 KB
 constexpr int PANEL_ROWS = 4;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// LDS-direct buffer load of 16 bytes per lane: lane l's bytes land at M0 + 16 l.  voff = per-lane byte offset from the
-// descriptor's base (range-checked against num_records: out-of-range lanes deliver zeros).  Inline assembly: the compiler
-// keeps no book on it (the kernel counts vmcnt itself); M0 is written in the statement that uses it.
-__device__ __forceinline__ void dma16(unsigned voff, u32x4 srd, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :: "v"(voff), "s"(srd), "s"(lds_dst) : "memory");
-}
-
-#define G8_BAR()                                     \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_sched_barrier(0);           \
-    } while (0)
 
 struct Coords { int z, mt, nt; };
 
@@ -107,14 +91,13 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
     const int total = n_items * ktn;                                           // K tiles in this workgroup's stream (< 2^31: host check)
 
     // ---- DMA source geometry of this thread: 2 wave-instructions per half-tile, each fills 8 LDS rows
-    //   instruction i of wave w fills LDS rows lr = (i*8 + w)*8 + (lane >> 3); slot s = lane & 7 holds chunk c = s ^ ((lr >> 1) & 7)
+    //   instruction i of wave w fills LDS rows lr = (i*8 + w)*8 + (lane >> 3); slot s = lane & 7 holds chunk c = s ^ swz_kc(lr)
     //   A half h: tile row i*128 + h*64 + w*8 + (lane >> 3);   B half h: tile column i*128 + h*32 + (w >> 2)*64 + (w & 3)*8 + (lane >> 3)
     const int lsub = lane >> 3;
-    const int ck = (lane & 7) ^ (((wave * 8 + lsub) >> 1) & 7);
+    const int ck = (lane & 7) ^ swz_kc(wave * 8 + lsub);
     const unsigned voffA = (unsigned)(((wave * 8 + lsub) * (int)p.lda) * ES + ck * 16);
     const unsigned voffB = (unsigned)((((wave >> 2) * 64 + (wave & 3) * 8 + lsub) * (int)p.ldb) * ES + ck * 16);
     const unsigned rowA = (unsigned)(64 * (int)p.lda * ES), rowB = (unsigned)(32 * (int)p.ldb * ES);   // per h; per i: 128 rows
-    typedef __attribute__((address_space(3))) unsigned int lds_u32_t;
     const unsigned smem_lds = (unsigned)(uintptr_t)(lds_u32_t*)smem;
     const unsigned dma_dst = smem_lds + (unsigned)(wave * 1024);               // + buf*STAGE + which*HALF + i*8192
 
@@ -162,13 +145,12 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
         dma16(v0, srd, dst);
         dma16(v0 + 2 * (isA ? rowA : 2 * rowB), srd, dst + 8192u);
     };
-    using C0 = std::integral_constant<int, 0>; using C1 = std::integral_constant<int, 1>;
-    using C2 = std::integral_constant<int, 2>; using C3 = std::integral_constant<int, 3>;
 
-    // ---- fragment read addresses: LDS row r = base + (lane & 15), chunk (kk*4 + (lane >> 4)) ^ ((r >> 1) & 7); the row
-    // bases are multiples of 16, so the swizzle term depends on the lane only; kk = 1 flips chunk bit 2 (byte 64)
+    // ---- fragment read addresses: LDS row r = base + (lane & 15), chunk (kk*4 + (lane >> 4)) ^ swz_kc(r); the row
+    // bases are multiples of 16, so the swizzle term depends on the lane only (swz_kc(r) = swz_kc(lane): it looks at bits
+    // 1-3); kk = 1 flips chunk bit 2 (byte 64)
     const int frow = lane & 15;
-    const unsigned fsw0 = (unsigned)((((lane >> 4) ^ ((frow >> 1) & 7)) << 4));
+    const unsigned fsw0 = (unsigned)((((lane >> 4) ^ swz_kc(lane)) << 4));
     const unsigned fA0 = (unsigned)((wm * 64 + frow) * 128) + fsw0;     // + i*2048 (16 rows); kk = 1: byte bit 6 flipped
     const unsigned fB0 = (unsigned)((wn * 32 + frow) * 128) + fsw0;     // + j*2048
     const unsigned fA1 = fA0 ^ 64u, fB1 = fB0 ^ 64u;
@@ -192,30 +174,28 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
             bf[j][1] = *reinterpret_cast<const bf16x8_t*>(base + fB1 + j * 2048);
         }
     };
-    // operands swapped (D = Bfrag . Afrag^T): a lane holds 4 consecutive output COLUMNS of one output row
-    //   acc[i8][j4][r]: row = wm*128 + i8*16 + (lane & 15), column = wn*64 + j4*16 + (lane >> 4)*4 + r
+    // one C quadrant; the accumulator layout is gt::mma_quad's.  fp8: a 16-byte fragment is two 8-byte MFMA operands
     auto mma_quad = [&](const bf16x8_t (&af)[4][2], const bf16x8_t (&bf)[2][2], auto ih_c, auto jh_c) __attribute__((always_inline)) {
         constexpr int ih = decltype(ih_c)::value, jh = decltype(jh_c)::value;
-        __builtin_amdgcn_s_setprio(1);
+        if constexpr (FP8) {
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
+            for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if constexpr (FP8) {
+                    for (int j = 0; j < 2; ++j) {
                         typedef __attribute__((ext_vector_type(2))) long l2_t;
                         const l2_t a2 = __builtin_bit_cast(l2_t, af[i][kk]), b2 = __builtin_bit_cast(l2_t, bf[j][kk]);
                         f32x4_t c = acc[ih * 4 + i][jh * 2 + j];
                         c = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[0], a2[0], c, 0, 0, 0);
                         c = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[1], a2[1], c, 0, 0, 0);
                         acc[ih * 4 + i][jh * 2 + j] = c;
-                    } else {
-                        acc[ih * 4 + i][jh * 2 + j] =
-                            MC_MFMA_16x16x32(bf[j][kk], af[i][kk], acc[ih * 4 + i][jh * 2 + j], 0, 0, 0);
                     }
-                }
-        __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
+        } else {
+            gt::mma_quad<ih, jh>(acc, af, bf);
+        }
     };
 
     // alpha_dev: a device-resident factor (the product of the fp8 dequantisation scales); pinned before the loop
@@ -238,13 +218,10 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
     stage(1, C2{}); stage(1, C0{}); stage(1, C3{});
     if (pd.valid) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    G8_BAR();
-    if (wm == 1) G8_BAR();                      // wave row 1 runs half a phase behind wave row 0 from here on
+    GT_BAR();
+    if (wm == 1) GT_BAR();                      // wave row 1 runs half a phase behind wave row 0 from here on
 
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    GT_CLEAR_ACC(acc);
 
     bool drain = false;                         // stores of an epilogue are in the queue: the next tile wait drains it
     int buf = 0;
@@ -257,27 +234,27 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
         stage(buf ^ 1, C1{});                                    // A1 of tile t+1
         prod_next();                                             // pd = tile t+2
         asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");       // the 4 B0 reads have retired (B0 is re-staged next phase)
-        G8_BAR();
+        GT_BAR();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         mma_quad(a0, b0, C0{}, C0{});
-        G8_BAR();
+        GT_BAR();
         // ------------------------------------------------ phase 2: quadrant (0,1)
         read_b(b1, buf, 1);
         stage(buf, C2{});                                        // B0 of tile t+2
-        G8_BAR();
+        GT_BAR();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         mma_quad(a0, b1, C0{}, C1{});
-        G8_BAR();
+        GT_BAR();
         // ------------------------------------------------ phase 3: quadrant (1,1)
         read_a(a1, buf, 1);
         stage(buf, C0{});                                        // A0 of tile t+2
-        G8_BAR();
+        GT_BAR();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         mma_quad(a1, b1, C1{}, C1{});
-        G8_BAR();
+        GT_BAR();
         // ------------------------------------------------ phase 4: quadrant (1,0)
         if (drain) {
             // first tile after an epilogue: its global stores share the counter with the DMAs and may complete out of
@@ -291,15 +268,15 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
             if (pd.valid) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");           // everything up to A1(t+1) has landed
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        G8_BAR();
+        GT_BAR();
         mma_quad(a1, b0, C1{}, C0{});
-        G8_BAR();
+        GT_BAR();
 
         buf ^= 1;
         ++ckt;
         if (ckt == ktn) {
             // ============================================ epilogue of item cc
-            if (wm == 0) G8_BAR();              // un-stagger: wave row 0 waits for wave row 1 to finish its last quadrant
+            if (wm == 0) GT_BAR();              // un-stagger: wave row 0 waits for wave row 1 to finish its last quadrant
             unsigned char* const etile = smem + EPI_OFF;
             const long long m0 = (long long)cc.mt * BM;
             const int n0 = cc.nt * BN;
@@ -354,7 +331,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
                             *reinterpret_cast<uint2*>(etile + row * (BN * 2) + ((ch ^ (row & 31)) << 4) + (col & 7) * 2) = pk;
                         }
                 }
-                G8_BAR();
+                GT_BAR();
                 if (ncol < p.N) {
                     // residual: the 4 vectors of this thread's slab rows in flight together, ONE wait (round 5; the first
                     // form paid 4 dependent round trips per slab).  Rows beyond M re-read row m0 (valid) and are not stored.
@@ -398,7 +375,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
                         }
                     }
                 }
-                G8_BAR();
+                GT_BAR();
             }
             if (STATS) {
                 // column statistics of this output tile: 16 row groups -> one value per column, fixed order
@@ -408,7 +385,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
                     red[(r0 * BN + c16 * 8 + q) * 2 + 0] = csum[q];
                     red[(r0 * BN + c16 * 8 + q) * 2 + 1] = csq[q];
                 }
-                G8_BAR();
+                GT_BAR();
                 if (tid < BN) {
                     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -420,20 +397,17 @@ __global__ __launch_bounds__(NTHR, 2) void gemm8p_kernel(const mc_gemm_args p, c
                         dst[p.N + n] = s2;
                     }
                 }
-                G8_BAR();
+                GT_BAR();
             }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            GT_CLEAR_ACC(acc);
             drain = true;
             ckt = 0;
             ++cit;
             if (cit < (unsigned)n_items) cc = item_coords(xcd, slot, S, NTl, MT, ux, pr, cit);
-            if (wm == 1) G8_BAR();              // restore the half-phase stagger
+            if (wm == 1) GT_BAR();              // restore the half-phase stagger
         }
     }
-    if (wm == 0) G8_BAR();                      // balance the extra barrier of wave row 1
+    if (wm == 0) GT_BAR();                      // balance the extra barrier of wave row 1
 }
 
 }  // namespace g8

@@ -9,43 +9,25 @@
 //   * a K tile is 64 ROWS of the operands; half h of A holds the 2 x 64 output rows (columns of the operand) of C-quadrant
 //     row h as [64 k][128 m] bf16 (256 bytes per k row), half h of B the 4 x 32 columns of quadrant column h
 //   * MFMA operand fragments come from the row-major image through gfx950's LDS transpose-read (ds_read_b64_tr_b16: a
-//     16-lane group reads a 4 (k) x 16 (m) block, lane c receives column c): two reads per fragment.  Conflict-free with
-//     the source-side swizzle "16-byte chunk c of k row r sits in slot c ^ 2((r & 3) | ((r >> 1) & 4))" -- the 8 k rows
-//     {8g .. 8g+3} U {8g+8 .. 8g+11} a 32-lane bank group touches land in 8 different 32-byte columns; XOR by an EVEN
-//     number keeps the 32-byte pairs a transpose-read needs together
+//     16-lane group reads a 4 (k) x 16 (m) block, lane c receives column c): two reads per fragment (gemm_tile.h's tr_read).
+//     Conflict-free with the source-side swizzle "16-byte chunk c of k row r sits in slot c ^ 2 swz_km(r)" (gemm_tile.h)
 //   * rows beyond the K range of a split deliver zeros through the descriptor's num_records; columns beyond M / N are one
 //     per-lane flag per output tile (bit 31 of the offset); nothing else distinguishes a partial tile
 //   * items = (output tile, K split); all tiles of one split run on ONE XCD at about the same time (they read the same
 //     slab of both operands); each item writes its fp32 tile straight from the accumulators (a lane owns 4 consecutive
 //     columns: 16-byte stores) into the split-K workspace, combined by gemm.hip's splitk_reduce_kernel (fixed order, optional
 //     per-(group, column) factor = the SE gate of the grouped form), or into C when there is one split.
-#include "common_hip.h"
-#include "../../include/mammoclip_hip.h"
+// The split's K range, the DMA, barrier, transpose-read, swizzle and MFMA-quadrant helpers come from gemm_tile.h; this file
+// keeps the TN staging geometry, the item order, the 4-phase loop, the fp32 epilogue and the host-side split / routing rules.
+#include "gemm_tile.h"
 
 namespace g8t {
+using namespace gt;
 
 constexpr int BM = 256, BN = 256, BK = 64, NTHR = 512;
 constexpr int HALF_BYTES = 64 * 256;             // 64 k rows of 256 bytes
 constexpr int STAGE_BYTES = 4 * HALF_BYTES;      // 64 KB: [A0 | A1 | B0 | B1]
 constexpr int LDS_BYTES = 2 * STAGE_BYTES;       // 128 KB
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((ext_vector_type(8))) short s8_t;
-typedef __attribute__((address_space(3))) s4_t lds_s4_t;
-
-__device__ __forceinline__ void dma16(unsigned voff, u32x4 srd, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :: "v"(voff), "s"(srd), "s"(lds_dst) : "memory");
-}
-
-#define G8T_BAR()                                    \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_sched_barrier(0);           \
-    } while (0)
 
 struct Item { int mt, nt, split; long long kbeg, kend; int ktn; };
 
@@ -73,19 +55,9 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
         q.split = by_split ? xcd + 8 * (int)sl : (int)sl;
         q.mt = (int)(tile / (unsigned)NT);
         q.nt = (int)(tile - (unsigned)q.mt * (unsigned)NT);
-        // K range of the split (same rule as gemm.hip's gemm_kernel: the workspace reduction is shared)
-        const long long ktiles = (p.K + BK - 1) / BK;
-        const long long tps = (ktiles + p.splits - 1) / p.splits;
-        q.kbeg = (long long)q.split * tps * BK;
-        q.kend = q.kbeg + tps * BK;
-        if (p.split_group_rows > 0) {
-            const long long grp = q.split / p.split_sub, j = q.split % p.split_sub;
-            const long long chunk = (p.split_group_rows + p.split_sub - 1) / p.split_sub;
-            q.kbeg = grp * p.split_group_rows + j * chunk;
-            q.kend = q.kbeg + chunk;
-            if (q.kend > (grp + 1) * p.split_group_rows) q.kend = (grp + 1) * p.split_group_rows;
-        }
-        if (q.kend > p.K) q.kend = p.K;
+        const KRange kr = split_k_range(p, q.split, BK);
+        q.kbeg = kr.kbeg;
+        q.kend = kr.kend;
         const long long len = q.kend - q.kbeg;
         q.ktn = len > 0 ? (int)((len + BK - 1) / BK) : 1;      // an empty split still owes its (zero) partial tile
         return q;
@@ -93,15 +65,14 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
 
     // ---- DMA source geometry: 2 wave-instructions per half-tile, each fills 4 k rows (1 KiB)
     //   instruction j = i*8 + wave covers k rows 4j + r, r = lane >> 4; LDS slot s = lane & 15 of the row's 256 bytes holds
-    //   source chunk c = s ^ fk, fk = 2 (r | ((wave & 2) << 1))    (= 2((k & 3) | ((k >> 1) & 4)) for k = 4j + r)
+    //   source chunk c = s ^ 2 swz_km(k), k = 4j + r = 4 wave + r (+ 32 i); of k, swz_km looks at bits 0, 1 (= r) and 3 (= wave & 2)
     //   A half h: chunk c -> operand column (c >> 3)*128 + h*64 + (c & 7)*8;   B half h: (c >> 2)*64 + h*32 + (c & 3)*8
     const int r4 = lane >> 4;
-    const int cs = (lane & 15) ^ (2 * (r4 | ((wave & 2) << 1)));
+    const int cs = (lane & 15) ^ (2 * swz_km(r4 | ((wave & 2) << 2)));
     const int colA = (cs >> 3) * 128 + (cs & 7) * 8, colB = (cs >> 2) * 64 + (cs & 3) * 8;      // + h*64 / h*32
     const unsigned voffA = (unsigned)((wave * 4 + r4) * (int)p.lda * 2 + colA * 2);
     const unsigned voffB = (unsigned)((wave * 4 + r4) * (int)p.ldb * 2 + colB * 2);
     const unsigned i1A = (unsigned)(32 * (int)p.lda * 2), i1B = (unsigned)(32 * (int)p.ldb * 2);  // second instruction: 32 k rows on
-    typedef __attribute__((address_space(3))) unsigned int lds_u32_t;
     const unsigned smem_lds = (unsigned)(uintptr_t)(lds_u32_t*)smem;
     const unsigned dma_dst = smem_lds + (unsigned)(wave * 1024);               // + buf*STAGE + which*HALF + i*8192
 
@@ -153,15 +124,13 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
         dma16(v0, srd, dst);
         dma16(v0 + (isA ? i1A : i1B), srd, dst + 8192u);
     };
-    using C0 = std::integral_constant<int, 0>; using C1 = std::integral_constant<int, 1>;
-    using C2 = std::integral_constant<int, 2>; using C3 = std::integral_constant<int, 3>;
 
     // ---- fragment read addresses (transpose-reads).  Lane (i = lane & 15, g = lane >> 4) supplies, for MFMA k step kk and
     // read half q2 (k rows 0-3 / 4-7 of its group of 8), the address of k row 32 kk + 8 g + 4 q2 + (i >> 2), bytes
     // ((blk * 32) ^ swz) + (i & 3) * 8 of that row, where blk = the fragment's 16-column block of the half-tile (A: wm*4 + ii,
-    // B: wn*2 + jj) and swz = 32 ((i >> 2) | ((g & 1) << 2)) -- the swizzle term does not depend on kk or q2.
+    // B: wn*2 + jj) and swz = 32 swz_km(8 g + (i >> 2)) -- the swizzle term does not depend on kk or q2.
     const int li = lane & 15, lg = lane >> 4;
-    const unsigned swz = (unsigned)(32 * ((li >> 2) | ((lg & 1) << 2)));
+    const unsigned swz = (unsigned)(32 * swz_km(8 * lg + (li >> 2)));
     const unsigned rowb = (unsigned)((8 * lg + (li >> 2)) * 256 + (li & 3) * 8);
     const unsigned fA = rowb + (((unsigned)(wm * 128)) ^ swz);      // ^ (ii << 5);  + kk*8192 + q2*1024
     const unsigned fB = rowb + (((unsigned)(wn * 64)) ^ swz);       // ^ (jj << 5)
@@ -169,12 +138,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
     f32x4_t acc[8][4];
     bf16x8_t a0[4][2], a1[4][2], b0[2][2], b1[2][2];
 
-    auto tr8 = [&](const unsigned char* ptr) __attribute__((always_inline)) {
-        const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ptr));
-        const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ptr + 1024));
-        const s8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8_t, v);
-    };
+    auto tr8 = [&](const unsigned char* ptr) __attribute__((always_inline)) { return tr_read(ptr, ptr + 1024); };   // 4 k rows on
     auto read_a2 = [&](bf16x8_t (&af)[4][2], int buf, int h, int i_lo) __attribute__((always_inline)) {
         const unsigned char* base = smem + buf * STAGE_BYTES + h * HALF_BYTES;
 #pragma unroll
@@ -191,21 +155,6 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
             bf[jj][1] = tr8(base + (fB ^ (unsigned)(jj << 5)) + 8192);
         }
     };
-    // operands swapped (D = Bfrag . Afrag^T): a lane holds 4 consecutive output COLUMNS of one output row
-    //   acc[i8][j4][r]: row = wm*128 + i8*16 + (lane & 15), column = wn*64 + j4*16 + (lane >> 4)*4 + r
-    auto mma_quad = [&](const bf16x8_t (&af)[4][2], const bf16x8_t (&bf)[2][2], auto ih_c, auto jh_c) __attribute__((always_inline)) {
-        constexpr int ih = decltype(ih_c)::value, jh = decltype(jh_c)::value;
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[ih * 4 + i][jh * 2 + j] =
-                        MC_MFMA_16x16x32(bf[j][kk], af[i][kk], acc[ih * 4 + i][jh * 2 + j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-    };
 
     unsigned cit = 0;
     int ckt = 0;
@@ -218,13 +167,10 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
     stage(1, C2{}); stage(1, C0{}); stage(1, C3{});
     if (pd.valid) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    G8T_BAR();
-    if (wm == 1) G8T_BAR();                     // wave row 1 runs half a phase behind wave row 0 from here on
+    GT_BAR();
+    if (wm == 1) GT_BAR();                     // wave row 1 runs half a phase behind wave row 0 from here on
 
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    GT_CLEAR_ACC(acc);
 
     bool drain = false;
     int buf = 0;
@@ -239,28 +185,28 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
         read_a2(a0, buf, 0, 2);                                  // 8
         stage(buf ^ 1, C1{});                                    // A1 of tile t+1
         prod_next();                                             // pd = tile t+2
-        G8T_BAR();
+        GT_BAR();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        mma_quad(a0, b0, C0{}, C0{});
-        G8T_BAR();
+        mma_quad<0, 0>(acc, a0, b0);
+        GT_BAR();
         // ------------------------------------------------ phase 2: quadrant (0,1)
         read_b(b1, buf, 1);
         stage(buf, C2{});                                        // B0 of tile t+2
-        G8T_BAR();
+        GT_BAR();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        mma_quad(a0, b1, C0{}, C1{});
-        G8T_BAR();
+        mma_quad<0, 1>(acc, a0, b1);
+        GT_BAR();
         // ------------------------------------------------ phase 3: quadrant (1,1)
         read_a2(a1, buf, 1, 0);
         read_a2(a1, buf, 1, 2);
         stage(buf, C0{});                                        // A0 of tile t+2
-        G8T_BAR();
+        GT_BAR();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        mma_quad(a1, b1, C1{}, C1{});
-        G8T_BAR();
+        mma_quad<1, 1>(acc, a1, b1);
+        GT_BAR();
         // ------------------------------------------------ phase 4: quadrant (1,0)
         if (drain) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // epilogue stores share the counter: nothing can be counted
@@ -271,9 +217,9 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
             if (pd.valid) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        G8T_BAR();
-        mma_quad(a1, b0, C1{}, C0{});
-        G8T_BAR();
+        GT_BAR();
+        mma_quad<1, 0>(acc, a1, b0);
+        GT_BAR();
 
         buf ^= 1;
         ++ckt;
@@ -301,7 +247,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm256_tn_kernel(const mc_gemm_args 
             ci = item_at(cit);
         }
     }
-    if (wm == 0) G8T_BAR();                     // balance the extra barrier of wave row 1
+    if (wm == 0) GT_BAR();                     // balance the extra barrier of wave row 1
 }
 
 }  // namespace g8t

@@ -1,5 +1,5 @@
-// Standalone micro-benchmark / phase profiler for the tiled GEMM (developer tool, not part of the library).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DGEMM_PROF] scripts/gemmbench.hip -o scripts/gemmbench.bin
+// Standalone micro-benchmark for the tiled GEMM (developer tool, not part of the library).
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/gemmbench.hip -o scripts/gemmbench.bin
 #include "../mammo_clip_amd/csrc/gemm.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -33,21 +33,12 @@ int main() {
         } else { a.lda = s.K; a.ldb = s.K; a.ldc = s.N; }
         if (mc_gemm_bf16(&a, nullptr)) { printf("err %s\n", mc_last_error()); return 1; }
         HC(hipDeviceSynchronize());
-#ifdef GEMM_PROF
-        unsigned long long z[8] = {0}; HC(hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_prof), z, sizeof(z)));
-#endif
         HC(hipEventRecord(e0));
         const int it = 5;
         for (int i = 0; i < it; ++i) mc_gemm_bf16(&a, nullptr);
         HC(hipEventRecord(e1)); HC(hipEventSynchronize(e1));
         float ms; HC(hipEventElapsedTime(&ms, e0, e1)); ms /= it;
         printf("%-5s M=%7lld N=%5d K=%7lld splits=%2d %7.3f ms %6.1f TF", s.kind, s.M, s.N, s.K, a.splits, ms, 2.0 * s.M * s.N * s.K / ms / 1e9);
-#ifdef GEMM_PROF
-        HC(hipMemcpyFromSymbol(z, HIP_SYMBOL(g_gemm_prof), sizeof(z)));
-        double tot = (double)(z[0] + z[1] + z[2] + z[3] + z[4]);
-        printf("  | store %4.1f%% barrier %4.1f%% issue %4.1f%% mfma %4.1f%% epilogue %4.1f%%  ksteps %llu cyc/step %.0f", 100 * z[0] / tot,
-               100 * z[1] / tot, 100 * z[2] / tot, 100 * z[3] / tot, 100 * z[4] / tot, z[5], tot / (z[5] ? z[5] : 1));
-#endif
         printf("\n");
     }
     return 0;

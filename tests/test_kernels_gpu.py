@@ -104,9 +104,14 @@ def test_gemm_wgrad_tn(M, N, K):
 
 
 class _force_gemm256_tn:
+    """MC_GEMM_256TN for the launches inside: 2 = the 256 x 256 TN kernel whenever the layout allows, 0 = never"""
+
+    def __init__(self, mode="2"):
+        self.mode = mode
+
     def __enter__(self):
         self.old = os.environ.get("MC_GEMM_256TN")
-        os.environ["MC_GEMM_256TN"] = "2"
+        os.environ["MC_GEMM_256TN"] = self.mode
 
     def __exit__(self, *a):
         if self.old is None:
@@ -146,6 +151,22 @@ def test_gemm256_tn_grouped_gate(n_img, hw, N, K):
         assert ops._tn256_plan(N, K, M, N, K, group_rows=hw) >= 1
         dw = ops.linear_wgrad(dy, x, pro=(None, None, gate, hw))
     check(dw, ref, 3e-3, "gemm256_tn grouped gate wgrad")
+
+
+@pytest.mark.parametrize("route", ["0", "2"])
+@pytest.mark.parametrize("M,N", [(136, 264), (40, 24)])
+def test_gemm_tn_empty_split(M, N, route):
+    """a split whose K range is empty still owes its (zero) partial tile: 9 K tiles of 64 rows over 4 splits give 3 tiles
+    per split, so split 3 starts at row 576 = K.  The workspace starts as NaN: a partial tile that is not written shows in
+    the sum.  Route 0 = the 128-row tile family (136 x 264: ragged direct-to-LDS tiles, 40 x 24: register-staged narrow
+    tiles), route 2 = the 256 x 256 TN kernel."""
+    K, splits = 576, 4
+    a, b = rnd(K, M, seed=21), rnd(K, N, seed=22)
+    ws = torch.full((splits, M, N), float("nan"), device=DEV, dtype=torch.float32)
+    c = torch.full((M, N), float("nan"), device=DEV, dtype=torch.float32)
+    with _force_gemm256_tn(route):
+        ops.gemm(a, b, c, M, N, K, M, N, N, a_kmajor=1, b_kmajor=1, c_f32=1, splits=splits, splitk_ws=ws)
+    check(c, a.float().T @ b.float(), 2e-3, f"tn empty split, route {route}")
 
 
 def test_gemm_prologue_a_and_b():
