@@ -624,11 +624,14 @@ int mc_grads_unscale(const mc_adamw_tensor* tensors, int n_tensors, float inv_sc
  *   mc_adamw_step_ls     : mc_adamw_step that does nothing when *found_inf != 0 and takes its bias corrections from the number
  *                          of APPLIED steps, step - *skipped (skipped = the optimizer's own device counter)
  *   mc_loss_scale_update : GradScaler.update(): consumes and clears the flag; scale *= backoff on a bad step, *= growth after
- *                          growth_interval clean ones (dynamic != 0); counts the skip in state[3] and in *opt_skipped */
+ *                          growth_interval clean ones (dynamic != 0); counts the skip in state[3] and in *opt_skipped.
+ *                          The scale does not grow past the fp32 range: a grown value that is not finite is dropped (the
+ *                          clean-step counter still returns to 0).  The factors are doubles and the product is rounded to
+ *                          fp32 once, which is torch's arithmetic bit for bit. */
 int mc_grads_unscale_dev(const mc_adamw_tensor* tensors, int n_tensors, const float* scale_dev, float* found_inf, void* stream);
 int mc_adamw_step_ls(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps,
                      double weight_decay, long long step, const float* found_inf, const float* skipped, void* stream);
-int mc_loss_scale_update(float* state, float* opt_skipped, float growth_factor, float backoff_factor, int growth_interval,
+int mc_loss_scale_update(float* state, float* opt_skipped, double growth_factor, double backoff_factor, int growth_interval,
                          int dynamic, void* stream);
 
 #ifdef __cplusplus

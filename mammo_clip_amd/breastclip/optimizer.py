@@ -5,7 +5,7 @@ that behaviour is kept.
 ``AdamW`` below is the hot loop's optimizer step: the same hyper-parameters, update rule
 and ``state_dict()`` layout as ``torch.optim.AdamW`` (state per parameter: ``step``, ``exp_avg``, ``exp_avg_sq``), so
 optimizer checkpoints move both ways [ref: trainer.py:215-237 stores ``optimizer.state_dict()``], with the update done
-by one multi-tensor HIP kernel per 48 parameters (``mc_adamw_step``)."""
+by one multi-tensor HIP kernel per 40 parameters (``mc_adamw_step``)."""
 from typing import Dict
 
 import torch
@@ -60,6 +60,10 @@ class AdamW(torch.optim.Optimizer):
             # new plan reads ``state[p]["step"]`` (applied counts) and must not have the same skips subtracted again, and a
             # group planned for the first time after some skips must not inherit them
             self._fold_skipped()
+        else:
+            # plain steps: the counts live in the plan that is being replaced; ``state[p]["step"]`` is only as fresh as the
+            # last state_dict() call, and a rebuilt plan (the set of parameters with a gradient changed) reads it below
+            self._sync_steps()
         steps = []
         arr = (L.AdamwTensor * max(len(params), 1))()
         for i, p in enumerate(params):

@@ -4,6 +4,7 @@
 // B5 + BERT model; a parameter that is consumed as a bf16 matrix gets its bf16 image rewritten by the same pass (+2 B)
 // instead of by a cast kernel of its own in the next forward.  Up to PACK tensors go into one launch (pointers travel as kernel arguments, no device
 // table to keep in sync); a workgroup owns one CHUNK of one tensor, found by a scan over the pack's chunk prefix.
+#include <cfloat>
 #include "common_hip.h"
 #include "../../include/mammoclip_hip.h"
 
@@ -134,6 +135,9 @@ struct UnscalePack {
     long long n[PACK];
 };
 
+// torch.isfinite's answer: +-FLT_MAX is a finite gradient, inf and nan (every compare with nan is false) are not
+__device__ __forceinline__ bool nonfinite(float v) { return !(fabsf(v) <= FLT_MAX); }
+
 __global__ void __launch_bounds__(256) grads_unscale_k(UnscalePack pk, int count, float inv_scale, const float* __restrict__ scale_dev,
                                                        float* __restrict__ found_inf) {
     if (scale_dev) inv_scale = 1.0f / *scale_dev;                       // the dynamic scale lives on the device (no host sync)
@@ -150,28 +154,35 @@ __global__ void __launch_bounds__(256) grads_unscale_k(UnscalePack pk, int count
         for (; i + 3 < len; i += 1024) {
             float4 v = *(const float4*)(g + i);
             v.x *= inv_scale; v.y *= inv_scale; v.z *= inv_scale; v.w *= inv_scale;
-            bad |= !(fabsf(v.x) <= 3.4e38f) || !(fabsf(v.y) <= 3.4e38f) || !(fabsf(v.z) <= 3.4e38f) || !(fabsf(v.w) <= 3.4e38f);
+            bad |= nonfinite(v.x) || nonfinite(v.y) || nonfinite(v.z) || nonfinite(v.w);
             *(float4*)(g + i) = v;
         }
         const int j = (len & ~3) + threadIdx.x;
-        if (j < len) { const float v = g[j] * inv_scale; bad |= !(fabsf(v) <= 3.4e38f); g[j] = v; }
+        if (j < len) { const float v = g[j] * inv_scale; bad |= nonfinite(v); g[j] = v; }
     } else {
-        for (int j = threadIdx.x; j < len; j += 256) { const float v = g[j] * inv_scale; bad |= !(fabsf(v) <= 3.4e38f); g[j] = v; }
+        for (int j = threadIdx.x; j < len; j += 256) { const float v = g[j] * inv_scale; bad |= nonfinite(v); g[j] = v; }
     }
     if (bad) *found_inf = 1.0f;          // (every writer stores the same value)
 }
 
 // GradScaler.update() on the device [ref: trainer_ddp.py:303]: state = {scale, clean steps in a row, found_inf flag of the
 // step, steps skipped (this scaler), _}.  Consumes and clears the flag; the optimizer's own skipped-step counter follows.
-__global__ void loss_scale_update_k(float* __restrict__ st, float* __restrict__ opt_skipped, float growth, float backoff, int interval, int dynamic) {
+// The arithmetic is torch's (amp_update_scale_cuda_kernel): the fp32 scale times the DOUBLE factor, rounded once -- with a
+// factor like 0.3 an fp32 multiply by 0.3f lands on other scales after two steps -- and a scale that growth would take
+// past the fp32 range stays where it is (an inf scale never comes back: inf * backoff = inf, every later step skipped).
+__global__ void loss_scale_update_k(float* __restrict__ st, float* __restrict__ opt_skipped, double growth, double backoff, int interval, int dynamic) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const bool bad = st[2] != 0.f;
     if (bad) { st[3] += 1.f; if (opt_skipped) *opt_skipped += 1.f; }
     if (dynamic) {
-        if (bad) { st[0] *= backoff; st[1] = 0.f; }
+        if (bad) { st[0] = (float)((double)st[0] * backoff); st[1] = 0.f; }
         else {
             st[1] += 1.f;
-            if (st[1] >= (float)interval) { st[0] *= growth; st[1] = 0.f; }
+            if (st[1] >= (float)interval) {
+                const float grown = (float)((double)st[0] * growth);
+                if (!nonfinite(grown)) st[0] = grown;
+                st[1] = 0.f;
+            }
         }
     }
     st[4] = bad ? 1.f : 0.f;        // what happened to the step just finished (for whoever looks, later)
@@ -191,9 +202,9 @@ extern "C" int mc_grads_unscale_dev(const mc_adamw_tensor* tensors, int n_tensor
     return grads_unscale_impl(tensors, n_tensors, 1.0f, scale_dev, found_inf, stream);
 }
 
-extern "C" int mc_loss_scale_update(float* state, float* opt_skipped, float growth_factor, float backoff_factor, int growth_interval,
+extern "C" int mc_loss_scale_update(float* state, float* opt_skipped, double growth_factor, double backoff_factor, int growth_interval,
                                     int dynamic, void* stream) {
-    MC_CHECK(state && growth_factor > 0.f && backoff_factor > 0.f && growth_interval >= 1, "loss_scale_update: bad arguments");
+    MC_CHECK(state && growth_factor > 0.0 && backoff_factor > 0.0 && growth_interval >= 1, "loss_scale_update: bad arguments");
     hipLaunchKernelGGL(loss_scale_update_k, dim3(1), dim3(64), 0, (hipStream_t)stream, state, opt_skipped, growth_factor, backoff_factor,
                        growth_interval, dynamic);
     MC_LAUNCH_CHECK();

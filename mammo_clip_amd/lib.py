@@ -101,7 +101,7 @@ _SIGS = {
     "mc_grads_unscale": ([C.POINTER(AdamwTensor), I, F, P, P], I),
     "mc_grads_unscale_dev": ([C.POINTER(AdamwTensor), I, P, P, P], I),
     "mc_adamw_step_ls": ([C.POINTER(AdamwTensor), I, D, D, D, D, D, LL, P, P, P], I),
-    "mc_loss_scale_update": ([P, P, F, F, I, I, P], I),
+    "mc_loss_scale_update": ([P, P, D, D, I, I, P], I),
     "mc_gemm_bf16": ([C.POINTER(GemmArgs), P], I),
     "mc_gemm_stat_rows": ([C.POINTER(GemmArgs)], I),
     "mc_gemm_tile_config": ([C.POINTER(GemmArgs)], I),

@@ -717,7 +717,7 @@ def test_sgemm_l2norm_ce():
 
 def test_adamw_multi_tensor_vs_torch():
     """row N2: mc_adamw_step against torch.optim.AdamW (the reference's optimizer, optimizer/__init__.py:28-29) over
-    ragged sizes (sub-vector, chunk-straddling, multi-chunk, > one 48-tensor launch), misaligned gradients (flat
+    ragged sizes (sub-vector, chunk-straddling, multi-chunk, > one 40-tensor launch), misaligned gradients (flat
     bucket views), a changing lr, and a state_dict hand-over in both directions.  fp32; a few ulp from operation order."""
     from mammo_clip_amd.breastclip.optimizer import AdamW
     torch.manual_seed(3)
@@ -759,6 +759,386 @@ def test_adamw_multi_tensor_vs_torch():
     om2.step(); ot2.step()
     for a, b in zip(mine, ref):
         torch.testing.assert_close(a, b, rtol=2e-6, atol=4e-7)
+
+
+# ---- the loss-scaled optimizer step (every step of the f16 storage build): mc_grads_unscale[_dev], mc_adamw_step_ls,
+# mc_loss_scale_update and their host bookkeeping (AdamW.step_loss_scaled, engine.LossScaler) against torch.optim.AdamW +
+# torch.amp.GradScaler.  All tensors fp32 on the device.  The common tensor set: sub-vector sizes, the last lane of the
+# vector body (1023 / 1024), a ragged tail (1027), a chunk of 16384 exactly, a second chunk of length 1, three chunks, and
+# 35 small tensors so that tensors 40 and up go into the second launch of a call (PACK = 40 in optim.hip).
+LS_SIZES = [1, 3, 4, 5, 1023, 1024, 1027, 16384, 16385, 2 * 16384 + 3] + [17 + i for i in range(35)]
+LS_LAYOUTS = ("own", "flat")
+LS_HYPER = (3e-3, 0.9, 0.999, 1e-8, 0.05)                  # lr, beta1, beta2, eps, weight_decay
+INF, NAN = float("inf"), float("nan")
+FLT_MAX = torch.finfo(torch.float32).max
+
+
+def _ls_normals(seed, scale=1.0, shapes=LS_SIZES):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return [torch.randn(s if isinstance(s, tuple) else (s,), generator=g) * scale for s in shapes]
+
+
+def _ls_place(host, layout):
+    """device copies of the host tensors: "own" = one allocation each (16-byte aligned: the kernels' vector path), "flat" =
+    views into one buffer that each start 4 bytes past a 16-byte boundary (scalar path)"""
+    if layout == "own":
+        out = [torch.empty_like(h, device=DEV).copy_(h) for h in host]
+    else:
+        offs, off = [], 1
+        for h in host:
+            offs.append(off)
+            off += (h.numel() + 3) // 4 * 4                # the next view starts at 1 (mod 4) again
+        flat = torch.zeros(off, device=DEV)
+        out = [flat[o:o + h.numel()].view(h.shape) for o, h in zip(offs, host)]
+        for o, h in zip(out, host):
+            o.copy_(h)
+    assert all((t.data_ptr() % 16 == 0) == (layout == "own") for t in out if t.numel())
+    return out
+
+
+def _ls_cat(ts):
+    return torch.cat([t.reshape(-1) for t in ts])
+
+
+def _ls_table(grad, param=None, exp_avg=None, exp_avg_sq=None, image=None):
+    """the mc_adamw_tensor table of a call, built like LossScaler._grad_table / AdamW._plan build theirs"""
+    arr = (L.AdamwTensor * max(len(grad), 1))()
+    for i, g in enumerate(grad):
+        a = arr[i]
+        a.grad, a.numel = g.data_ptr(), g.numel()
+        if param is not None:
+            a.param, a.exp_avg, a.exp_avg_sq = param[i].data_ptr(), exp_avg[i].data_ptr(), exp_avg_sq[i].data_ptr()
+        if image is not None and image[i] is not None:
+            a.bf16_image = image[i].data_ptr()
+    return arr
+
+
+def _ls_unscale(entry, arr, n, scale, flag):
+    if entry == "mc_grads_unscale":                        # the host hands over 1 / scale, rounded once to fp32
+        L.call(entry, arr, n, 1.0 / scale, flag.data_ptr(), ops._st())
+    else:                                                  # the kernel divides by the device scale itself
+        sc = torch.tensor([scale], dtype=torch.float32, device=DEV)
+        L.call(entry, arr, n, sc.data_ptr(), flag.data_ptr(), ops._st())
+        torch.cuda.synchronize()                           # (sc is read through a raw pointer)
+
+
+LS_UNSCALE_ENTRIES = ("mc_grads_unscale", "mc_grads_unscale_dev")
+
+
+@pytest.mark.parametrize("entry", LS_UNSCALE_ENTRIES)
+@pytest.mark.parametrize("layout", LS_LAYOUTS)
+def test_grads_unscale_values(layout, entry):
+    """grad *= 1 / scale over the common tensor set, gradients = seeded normals * 10^k.  A power-of-two scale (2^16, 2^-3)
+    makes 1 / scale and the product exact: BIT-equal to torch's fp32 g * (1 / scale).  Scale 3000: within 4 fp32 ulp of the
+    fp64 quotient, rtol 4 * 2^-23 = 4.8e-7 -- derived, not measured: one rounding in the reciprocal (1/2 ulp, on the host
+    for mc_grads_unscale, a correctly rounded or at worst 2.5-ulp device division for mc_grads_unscale_dev), one in the
+    product (1/2 ulp), the rest is headroom for the compiler's default fp32 division.  Zero-element tensors in the table
+    (first, across the 40-tensor launch boundary, last) are skipped; n_tensors = 0 is a no-op that returns OK."""
+    flag = torch.zeros(1, device=DEV)
+    hole = torch.empty(0)
+    for k in (-3, 0, 3):
+        host = _ls_normals(40 + k, 10.0 ** k)
+        host = [hole] + host[:39] + [hole] + host[39:] + [hole]
+        src = _ls_cat(host).to(DEV)
+        for scale in (2.0 ** 16, 2.0 ** -3, 3000.0):
+            g = _ls_place(host, layout)
+            _ls_unscale(entry, _ls_table(g), len(g), scale, flag)
+            got = _ls_cat(g)
+            if scale == 3000.0:
+                torch.testing.assert_close(got.double(), src.double() / 3000.0, rtol=4.8e-7, atol=0.0)
+            else:
+                assert torch.equal(got, src * torch.tensor(1.0 / scale, dtype=torch.float32, device=DEV)), (k, scale)
+            assert flag.item() == 0.0, (k, scale)
+    g = _ls_place(_ls_normals(41), layout)
+    want = _ls_cat(g).clone()
+    _ls_unscale(entry, _ls_table(g), 0, 2.0, flag)                        # an empty call: nothing is touched
+    if entry == "mc_grads_unscale":
+        L.call(entry, None, 0, 0.5, flag.data_ptr(), ops._st())
+    assert torch.equal(_ls_cat(g), want) and flag.item() == 0.0
+
+
+# (tensor, element) of the one non-finite value: the 1-element tensor; the last lane of the vector body; the ragged tail
+# after the last whole float4 (first and last element of it); a second chunk of length 1; the last element of the third
+# chunk; the 45th tensor of the table, which the second launch of the call owns
+LS_BAD_AT = [(0, 0), (5, 1023), (6, 1024), (6, 1026), (8, 16384), (9, 2 * 16384 + 2), (44, 10)]
+
+
+@pytest.mark.parametrize("layout", LS_LAYOUTS)
+def test_grads_unscale_flag(layout):
+    """the non-finite flag against torch.isfinite: exactly 1.0 for one +inf / -inf / nan at every position of LS_BAD_AT (each
+    value at each position, both entries, so every value meets the vector body, the ragged tail and the scalar path), every
+    other element still unscaled BIT-exactly (scale 2^16); exactly 0.0 for finite gradients, +-FLT_MAX (scale 1) and fp32
+    denormals included; a flag the caller left at 1 stays 1 (the launches of one call share it, the caller clears it)."""
+    host = _ls_normals(50)
+    g = _ls_place(host, layout)
+    arr, n = _ls_table(g), len(g)
+    clean = [t.clone() for t in g]
+    starts = [0]
+    for h in host:
+        starts.append(starts[-1] + h.numel())
+    flag = torch.zeros(1, device=DEV)
+    scale = 2.0 ** 16
+    ref = _ls_cat(clean) * torch.tensor(1.0 / scale, dtype=torch.float32, device=DEV)
+    assert torch.isfinite(ref).all()
+    for entry in LS_UNSCALE_ENTRIES:
+        for ti, ei in LS_BAD_AT:
+            assert ei < host[ti].numel()
+            for bad in (INF, -INF, NAN):
+                torch._foreach_copy_(g, clean)
+                flag.zero_()
+                g[ti][ei] = bad
+                assert not torch.isfinite(_ls_cat(g)).all()
+                _ls_unscale(entry, arr, n, scale, flag)
+                got, at = _ls_cat(g), starts[ti] + ei
+                assert flag.item() == 1.0, (entry, ti, ei, bad)
+                v = got[at].item()
+                assert v == bad or (bad != bad and v != v), (entry, ti, ei, bad, v)
+                got[at] = ref[at]
+                assert torch.equal(got, ref), (entry, ti, ei, bad)
+    edge = {(0, 0): FLT_MAX, (5, 0): FLT_MAX, (5, 1023): -FLT_MAX, (6, 1024): FLT_MAX, (6, 1026): -FLT_MAX, (8, 16384): FLT_MAX,
+            (9, 2 * 16384 + 2): -FLT_MAX, (44, 10): FLT_MAX, (7, 5): 1e-40, (6, 1025): -1e-40}
+    for entry in LS_UNSCALE_ENTRIES:
+        torch._foreach_copy_(g, clean)
+        flag.zero_()
+        for (ti, ei), val in edge.items():
+            g[ti][ei] = val
+        want = _ls_cat(g).clone()
+        assert torch.isfinite(want).all() and (want.abs() == FLT_MAX).sum() == 8 and ((want != 0) & (want.abs() < 1e-38)).sum() == 2
+        _ls_unscale(entry, arr, n, 1.0, flag)
+        assert flag.item() == 0.0, entry                                  # torch.isfinite(want).all() says: clean
+        assert torch.equal(_ls_cat(g), want), entry
+        torch._foreach_copy_(g, clean)
+        flag.fill_(1.0)
+        _ls_unscale(entry, arr, n, scale, flag)
+        assert flag.item() == 1.0 and torch.equal(_ls_cat(g), ref), entry
+
+
+def _ls_adam_state(layout, seed):
+    """param / grad / exp_avg / exp_avg_sq over a 2-D tensor, the common set and another 2-D tensor (47 tensors: 40 + 7),
+    each 2-D parameter with a bf16 image.  exp_avg_sq >= max(exp_avg^2, grad^2), so that the updated moments keep
+    |exp_avg| <= 1.0006 sqrt(exp_avg_sq) (Cauchy-Schwarz on 0.9 m + 0.1 g) like moments that come from real gradients."""
+    shapes = [(43, 47)] + LS_SIZES + [(5, 7)]
+    hp, hg, hm = _ls_normals(seed, 1.0, shapes), _ls_normals(seed + 1, 1.0, shapes), _ls_normals(seed + 2, 0.5, shapes)
+    hv = [torch.maximum(m * m, g * g) * (1.0 + r.abs()) for m, g, r in zip(hm, hg, _ls_normals(seed + 3, 1.0, shapes))]
+    host = (hp, hg, hm, hv)
+    p, g, m, v = (_ls_place(h, layout) for h in host)
+    image = [ops.cast_bf16(t) if t.dim() == 2 else None for t in p]
+    return host, (p, g, m, v), image, _ls_table(g, p, m, v, image)
+
+
+@pytest.mark.parametrize("layout", LS_LAYOUTS)
+def test_adamw_step_ls_kernel(layout):
+    """mc_adamw_step_ls.  Flag at 1: param, exp_avg, exp_avg_sq and the bf16 images are BIT-unchanged, for the tensors of both
+    launches.  Flag at 0, host step t, device counter s: compared with mc_adamw_step(step = max(t - s, 1)) on a copy of the
+    same state -- exp_avg / exp_avg_sq bit-equal (they do not depend on the bias scalars), param within one fp32 ulp, rtol
+    2^-23 and atol 2^-22 * lr.  Derived: the two kernels run the same instructions and differ only in the last bit of
+    step_size and 1 / sqrt(bias2), formed in double on the device instead of on the host (pow is not correctly rounded on
+    either).  That moves the update u = step_size * m / denom by <= 2 * 2^-23 |u| plus three roundings of 2^-24 |u|, and
+    |u| <= 0.32 * lr here (sqrt(bias2) / bias1 <= 0.316 for every applied step count, |m| <= 1.0006 sqrt(v)): < 2^-22 * lr;
+    the final rounding of param - u adds one ulp of param, the rtol.  Bad arguments raise and launch nothing."""
+    host, (p, g, m, v), image, arr = _ls_adam_state(layout, 60)
+    n = len(p)
+    flag, skipped = torch.zeros(1, device=DEV), torch.zeros(1, device=DEV)
+    lr = LS_HYPER[0]
+
+    def reset():
+        for dst, src in zip((p, g, m, v), host):
+            for d, s in zip(dst, src):
+                d.copy_(s)
+
+    def snap():
+        return [_ls_cat(x).clone() for x in (p, m, v)] + [im.clone() for im in image if im is not None]
+
+    before = snap()
+    flag.fill_(1.0)
+    L.call("mc_adamw_step_ls", arr, n, *LS_HYPER, 3, flag.data_ptr(), skipped.data_ptr(), ops._st())
+    assert all(torch.equal(a, b) for a, b in zip(snap(), before)), "a flagged step wrote something"
+    assert flag.item() == 1.0 and skipped.item() == 0.0
+    for t, s in [(1, 0), (5, 0), (5, 2), (9, 8), (3, 3), (2, 5)]:
+        reset()
+        flag.zero_()
+        skipped.fill_(float(s))
+        L.call("mc_adamw_step_ls", arr, n, *LS_HYPER, t, flag.data_ptr(), skipped.data_ptr(), ops._st())
+        got = snap()
+        assert flag.item() == 0.0 and skipped.item() == float(s)         # the kernel only reads them
+        for im, q in zip((im for im in image if im is not None), (q for q in p if q.dim() == 2)):
+            assert torch.equal(im, q.to(BF)), (t, s)
+        reset()
+        L.call("mc_adamw_step", arr, n, *LS_HYPER, max(t - s, 1), ops._st())
+        want = snap()
+        assert not torch.equal(want[0], before[0])
+        assert torch.equal(got[1], want[1]) and torch.equal(got[2], want[2]), (t, s)
+        torch.testing.assert_close(got[0], want[0], rtol=2.0 ** -23, atol=2.0 ** -22 * lr, msg=lambda m_: f"(t, s) = {(t, s)}: {m_}")
+    reset()
+    torch.cuda.synchronize()
+    before = snap()
+    st = torch.tensor([1024.0, 1, 0, 2, 0, 0, 0, 0], dtype=torch.float32, device=DEV)
+    for bad in [lambda: L.call("mc_adamw_step_ls", arr, n, *LS_HYPER, 2, None, skipped.data_ptr(), ops._st()),
+                lambda: L.call("mc_adamw_step_ls", arr, n, *LS_HYPER, 2, flag.data_ptr(), None, ops._st()),
+                lambda: L.call("mc_loss_scale_update", st.data_ptr(), skipped.data_ptr(), 2.0, 0.5, 0, 1, ops._st()),
+                lambda: L.call("mc_loss_scale_update", st.data_ptr(), skipped.data_ptr(), 0.0, 0.5, 3, 1, ops._st()),
+                lambda: L.call("mc_loss_scale_update", st.data_ptr(), skipped.data_ptr(), 2.0, -0.5, 3, 1, ops._st()),
+                lambda: L.call("mc_loss_scale_update", None, skipped.data_ptr(), 2.0, 0.5, 3, 1, ops._st())]:
+        with pytest.raises(L.MammoClipHipError):
+            bad()
+    assert all(torch.equal(a, b) for a, b in zip(snap(), before))
+    assert st.tolist() == [1024.0, 1, 0, 2, 0, 0, 0, 0] and skipped.item() == 5.0
+
+
+LS_FLAGS = [0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0]      # an overflow one step before growth, two in a row, two growths
+
+
+def _gradscaler_trace(flags, init_scale, growth, backoff, interval):
+    """(scale, clean steps in a row) after every update of a torch.amp.GradScaler on the device that sees ``flags``"""
+    w = torch.nn.Parameter(torch.zeros(2, device=DEV))
+    opt = torch.optim.AdamW([w], foreach=False)
+    sc = torch.amp.GradScaler("cuda", init_scale=init_scale, growth_factor=growth, backoff_factor=backoff, growth_interval=interval)
+    sc.scale(torch.zeros((), device=DEV))
+    out = []
+    for f in flags:
+        w.grad = torch.full_like(w, INF if f else 0.0)
+        sc.step(opt)
+        sc.update()
+        out.append((sc.get_scale(), int(sc.state_dict()["_growth_tracker"])))
+    return out
+
+
+def _policy_trace(flags, init_scale, growth, backoff, interval, dynamic=1, with_opt=True):
+    """the 8 state floats (+ the optimizer's counter) after every mc_loss_scale_update that sees ``flags``"""
+    st = torch.tensor([init_scale, 0, 0, 0, 0, 0, 0, 0], dtype=torch.float32, device=DEV)
+    osk = torch.zeros(1, device=DEV) if with_opt else None
+    out = []
+    for f in flags:
+        st[2] = float(f)
+        L.call("mc_loss_scale_update", st.data_ptr(), osk.data_ptr() if with_opt else None, growth, backoff, interval, dynamic,
+               ops._st())
+        out.append(st.tolist() + [osk.item() if with_opt else None])
+    return out
+
+
+@pytest.mark.parametrize("growth,backoff,with_opt", [(2.0, 0.5, True), (1.5, 0.3, True), (2.0, 0.5, False)])
+def test_loss_scale_policy_vs_gradscaler(growth, backoff, with_opt):
+    """mc_loss_scale_update against torch.amp.GradScaler("cuda", growth_interval=3) over LS_FLAGS: scale and clean-step
+    counter BIT-equal after every update (torch multiplies the fp32 scale by its double factor and rounds once; so does the
+    kernel), state[2] consumed, state[3] the running skip count, state[4] the outcome of the step, *opt_skipped follows."""
+    ref = _gradscaler_trace(LS_FLAGS, 1024.0, growth, backoff, 3)
+    assert len({s for s, _ in ref}) >= 3 and [t for _, t in ref].count(0) >= 5      # (the script moves the reference)
+    got = _policy_trace(LS_FLAGS, 1024.0, growth, backoff, 3, with_opt=with_opt)
+    for i, (row, (scale, tracker)) in enumerate(zip(got, ref)):
+        nskip = float(sum(LS_FLAGS[:i + 1]))
+        assert row[:5] == [scale, float(tracker), 0.0, nskip, float(LS_FLAGS[i])], (i, row, scale, tracker)
+        assert row[5:8] == [0.0, 0.0, 0.0] and row[8] == (nskip if with_opt else None), (i, row)
+
+
+def test_loss_scale_policy_static_and_range_bound():
+    """dynamic = 0: scale and counter never move, skips are still counted and the flag is still consumed.  Range bound: from
+    2^127 with growth_interval = 1 the scale stays 2^127 (GradScaler does not grow it to inf, after which every later step
+    would be skipped) and the counter returns to 0, equal to torch."""
+    for i, row in enumerate(_policy_trace(LS_FLAGS, 1024.0, 2.0, 0.5, 3, dynamic=0)):
+        nskip = float(sum(LS_FLAGS[:i + 1]))
+        assert row == [1024.0, 0.0, 0.0, nskip, float(LS_FLAGS[i]), 0.0, 0.0, 0.0, nskip], (i, row)
+    ref = _gradscaler_trace([0, 0, 0], 2.0 ** 127, 2.0, 0.5, 1)
+    got = _policy_trace([0, 0, 0], 2.0 ** 127, 2.0, 0.5, 1)
+    print("range bound: torch", ref, "kernel", [r[:2] for r in got])
+    for row, (scale, tracker) in zip(got, ref):
+        assert math.isfinite(row[0]) and row[0] == 2.0 ** 127 and row[1] == 0.0, row
+        assert row[:2] == [scale, float(tracker)], (row, scale, tracker)
+
+
+def test_loss_scaled_steps_vs_torch_gradscaler():
+    """The three launches and the host bookkeeping together: AdamW.step_loss_scaled + engine.LossScaler(1024, interval 4)
+    against torch.optim.AdamW + torch.amp.GradScaler over 24 steps on the common tensor set plus a 2-D parameter with a
+    cached bf16 image.  Both sides get the same scaled gradients (seeded normals * the reference scaler's scale, a changing
+    lr); an inf lands in one gradient on steps 1 (early), 6 and 7 (in a row), 11 (the step that would have grown the scale),
+    14, 17 and 22.  After every step: parameters at the plain kernel's tolerances (rtol 2e-6, atol 2e-7), scale and
+    clean-step counter bit-equal to GradScaler's, the image bit-equal to param.to(BF).  After 12 steps state_dict() holds
+    the APPLIED step count (8) on both sides and each optimizer continues from the other's state (load_state_dict and
+    _sync_steps under a non-zero device counter); on steps 16 and 17 one parameter has no gradient (the plan is rebuilt
+    while the device counter is non-zero: _fold_skipped; afterwards that parameter's count lags: the per-step-count launch
+    loop with the loss-scale tail); two plain step() calls at the end fold the counter at the top of step(), the second of
+    them again without that parameter's gradient: a plan rebuilt between plain steps must carry on from the counts of the
+    plan it replaces, not from the step counts of the last state_dict() call."""
+    from mammo_clip_amd import engine
+    from mammo_clip_amd.breastclip.optimizer import AdamW
+    shapes = LS_SIZES + [(43, 47)]
+    mine = [torch.nn.Parameter(h.to(DEV)) for h in _ls_normals(70, 1.0, shapes)]
+    ref = [torch.nn.Parameter(p.detach().clone()) for p in mine]
+    kw = dict(lr=3e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05)
+    om, ot = AdamW(mine, **kw), torch.optim.AdamW(ref, foreach=False, **kw)
+    sm = engine.LossScaler(init_scale=1024.0, growth_interval=4)
+    st = torch.amp.GradScaler("cuda", init_scale=1024.0, growth_interval=4)
+    st.scale(torch.zeros((), device=DEV))
+    bad_at = {1: 4, 6: 0, 7: 9, 11: 44, 14: 6, 17: 8, 22: 45}             # step -> the tensor whose gradient gets the inf
+    lagging, no_grad_steps = 7, (16, 17, 25)
+    offs, off = [], 1
+    for p in mine:
+        offs.append(off)
+        off += (p.numel() + 3) // 4 * 4
+    flat = torch.zeros(off, device=DEV)
+    big, img0 = mine[-1], ops.cast_bf16(mine[-1])
+    need, applied, growths = [], 0, 0
+
+    def set_grads(step, scale):
+        gen = torch.Generator(device=DEV).manual_seed(200 + step)
+        for i, (a, b) in enumerate(zip(mine, ref)):
+            v = flat[offs[i]:offs[i] + a.numel()].view_as(a)              # 4 bytes off a 16-byte boundary
+            v.copy_(torch.randn(a.shape, device=DEV, generator=gen) * (10.0 ** (step % 3 - 1) * scale))
+            if bad_at.get(step) == i:
+                v.view(-1)[v.numel() // 2] = INF
+            a.grad = v if step % 2 else v.clone()
+            b.grad = v.clone()
+            if step in no_grad_steps and i == lagging:
+                a.grad = b.grad = None
+
+    def compare(step, atol=2e-7):
+        a, b = _ls_cat([p.detach() for p in mine]), _ls_cat([p.detach() for p in ref])
+        assert torch.isfinite(a).all(), step
+        need.append(float(((a - b).abs() - 2e-6 * b.abs()).max()))     # the atol this step needs next to rtol 2e-6
+        img = ops.cast_bf16(big)
+        assert img is img0 and torch.equal(img, big.detach().to(BF)), step
+
+    for step in range(24):
+        if step == 12:
+            sdm, sdt = om.state_dict(), ot.state_dict()
+            assert int(om._ls_skipped.item()) == 4
+            for i in range(len(mine)):
+                assert float(sdm["state"][i]["step"]) == float(sdt["state"][i]["step"]) == 8.0, i
+            om, ot = AdamW(mine, **kw), torch.optim.AdamW(ref, foreach=False, **kw)
+            om.load_state_dict(sdt)
+            ot.load_state_dict(sdm)
+        scale, tracker = st.get_scale(), int(st.state_dict()["_growth_tracker"])
+        if step == 11:
+            assert tracker == 3                                           # a clean step 11 would have grown the scale
+        set_grads(step, scale)
+        for o in (om, ot):
+            o.param_groups[0]["lr"] = 3e-3 * (0.5 + 0.1 * (step % 7))
+        sm.unscale_(mine)
+        sm.update(om.step_loss_scaled(sm))
+        st.step(ot)
+        st.update()
+        applied += step not in bad_at
+        growths += st.get_scale() > scale
+        assert sm.scale == st.get_scale() and sm.state_dict()["growth_tracker"] == int(st.state_dict()["_growth_tracker"]), step
+        assert sm.skipped == step + 1 - applied and sm.last_skipped == (step in bad_at), step
+        compare(step)
+        if step in (16, 18):                                              # a plan rebuilt under a non-zero device counter
+            assert int(om._ls_skipped.item()) == 0
+    assert applied == 17 and growths == 2
+    sdm, sdt = om.state_dict(), ot.state_dict()
+    for i in range(len(mine)):
+        assert float(sdm["state"][i]["step"]) == float(sdt["state"][i]["step"]) == (16.0 if i == lagging else 17.0), i
+    assert int(om._ls_skipped.item()) == 1                                # step 22, not folded yet
+    for step in (24, 25):                             # plain steps on unscaled gradients; 25 rebuilds the plan once more
+        set_grads(step, 1.0)
+        om.step()
+        ot.step()
+        compare(step)
+    print("atol needed next to rtol 2e-6, per step:", " ".join(f"{x:.1e}" for x in need))
+    assert max(need) <= 2e-7, need
+    sdm, sdt = om.state_dict(), ot.state_dict()
+    for i, (a, b) in enumerate(zip(mine, ref)):
+        torch.testing.assert_close(om.state[a]["exp_avg_sq"], ot.state[b]["exp_avg_sq"], rtol=2e-6, atol=1e-12)
+        assert float(sdm["state"][i]["step"]) == float(sdt["state"][i]["step"]) == (17.0 if i == lagging else 19.0), i
 
 
 def test_raw_u8_input_pipeline_matches_host_normalisation():
