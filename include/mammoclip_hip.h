@@ -279,6 +279,23 @@ int mc_dwconv_bwd_data_stat_rows(const mc_dwconv_args* args);
 int mc_dwconv_fwd(const mc_dwconv_args* args, void* stream);
 int mc_dwconv_bwd_data(const mc_dwconv_args* args, void* stream);
 int mc_dwconv_bwd_weight(const mc_dwconv_args* args, void* stream);
+/* The E-free form of mc_dwconv_bwd_data for a STRIDE-2 3x3 conv whose input was silu(bn0(e))
+ * [ref: efficientnet_custom.py:104-111 backwards: _depthwise_conv, _bn0 + swish, with e = _expand_conv(x)]: with args->xw
+ * (+ cin <= 64, cin % 8 == 0) the launch does not READ e: epi_x is the block input x [n,h,w,cin] and e = x . xw^T is formed on
+ * the MFMA unit for the pixels the launch completes (raw e rounded once to 16 bits like the tensor the expand GEMM stores, the
+ * rule of mc_dwconv_bwd_fused below).  out = dZ0 and stat_partials (mc_dwconv_bwd_data_stat_rows() rows, the same count with
+ * and without xw) are what the e-reading launch leaves.  With args->dw_out the same launch is also the conv's weight gradient:
+ * f32 [k*k][c], accumulated into (+=) in the conv's own tap order, dW[kh,kw,c] += dD[o,j,c] * a0[2o-pt+kh, 2j-pl+kw, c] with
+ * a0 = silu(bn0(e)) (dw_out without xw is refused).  Together with mc_mbconv_xdw_fwd and the folded BatchNorm0 backward the
+ * expanded tensor of such a block is then neither rebuilt nor read in the backward.
+ * _supported: 3x3, stride 2, c % 8 == 0, epi_x and xw given, cin % 8 == 0, cin <= 64 (pointers are only tested for NULL).
+ * _preferred: the shapes on which the launch measured faster than the three it replaces. */
+int mc_dwconv_bwd_data_xw_supported(const mc_dwconv_args* args);
+/* how the stride-2 epilogue launch (with or without xw) splits its work: plan[4] = column strips per row, row segments per
+ * image, super-rows (2 input rows) per segment, channel tiles; returns mc_dwconv_bwd_data_stat_rows().  For tests that must
+ * know a shape spans several strips / segments. */
+int mc_dwconv_bwd_data_plan(const mc_dwconv_args* args, int* plan);
+int mc_dwconv_bwd_data_xw_preferred(const mc_dwconv_args* args);
 /* Two device forms of the forward / stride-1 data gradient exist: the "marching" kernels (a lane owns 2-4 channels, taps
  * in VGPRs) and the "lane = column" kernels of round 4 (a wave owns one channel pair, taps in SGPRs, 16-wave workgroups;
  * conv_lane.hip).  mc_dwconv_fwd picks by shape (5x5 from 50 output columns up); this switch overrides the choice for

@@ -383,7 +383,7 @@ class _MBConvFn(torch.autograd.Function):
         dy = dy.contiguous()
         x, e, d, p, act1, link, pro0 = sv["x"], sv["e"], sv["d"], sv["p"], sv["act1"], sv["link"], sv["pro0"]
         st0, st1, st2, gate, pooled = sv["st0"], sv["st1"], sv["st2"], sv["gate"], sv["pooled"]
-        if a.expand != 1 and e is None and not pl.efree:     # (recompute modes: same kernels, statistics epilogues off)
+        if a.expand != 1 and e is None and not (pl.efree or pl.efree_s2):     # (recompute modes: same kernels, statistics epilogues off)
             e = _expand_conv(pl, x, sv["we"], stats=False)[0]
         if d is None:
             d = _depthwise(blk, pl, x, e, sv["we"], sv["wkkc"], pro0, stats=False)[0]
@@ -427,7 +427,7 @@ class _MBConvFn(torch.autograd.Function):
         # round 5: stride-1 3x3 blocks run the WHOLE depthwise backward as one launch (conv_lane.hip MODE 3): data gradient with
         # the bn0 + swish epilogue AND the weight gradient from one staging of (dd, e) -- 3 passes over the expanded tensor
         # instead of 5; where that launch is not preferred: weight gradient + data gradient as two launches
-        if not pl.fused_dw:
+        if not (pl.fused_dw or pl.efree_s2):
             dwdw = ops.dwconv_bwd_weight(dw_in, dd, *pl.dw, pro=pro0)
         grads = {}
         if a.expand != 1:
@@ -439,6 +439,10 @@ class _MBConvFn(torch.autograd.Function):
             if pl.fused_dw:
                 dz0, part0, dwdw = ops.dwconv_bwd_fused(dd, e, st0, wflip, n, h, w, a.cexp, k, l, t, oh, ow,
                                                         xw=(x, sv["we"]) if pl.efree else None)
+            elif pl.efree_s2:
+                # stride-2 3x3 blocks in the recompute modes: e is neither rebuilt nor read -- the data-gradient launch forms
+                # the e rows of the pixels it completes from x and is the weight gradient too (three launches -> one)
+                dz0, part0, dwdw = ops.dwconv_bwd_data(dd, sv["wkkc"], *pl.dw, epi=(None, st0), xw=(x, sv["we"]), dw=True)
             else:
                 dz0, part0 = ops.dwconv_bwd_data(dd, sv["wkkc"], *pl.dw, w_kkc_flipped=wflip, epi=(e, st0))
             del dd
@@ -563,7 +567,7 @@ class _Conv(nn.Conv2d):
 _Geo = namedtuple("_Geo", ["idx", "expand", "k", "s", "cin", "cexp", "cout", "cse", "pad", "skip"])
 # one call of an MBConv block (MBConvBlock.plan); dw = (n, h, w, cexp, k, s, pad_l, pad_t, oh, ow), the argument run of ops.dwconv_*
 _Plan = namedtuple("_Plan", ["n", "h", "w", "oh", "ow", "training", "xdw", "efree", "fp8_expand", "keep_act", "fp8_project",
-                             "store_e", "store_d", "store_p", "fuse_proj_dgrad", "fused_dw", "fold_bn0", "xbwd", "dw"])
+                             "store_e", "store_d", "store_p", "fuse_proj_dgrad", "fused_dw", "fold_bn0", "xbwd", "dw", "efree_s2"])
 
 
 class MBConvBlock(nn.Module):
@@ -637,11 +641,15 @@ class MBConvBlock(nn.Module):
             fused_dw = efree or bool(FUSE_DW_BWD and expand and ops.dwconv_bwd_fused_ok(*dw))
             fold = expand and (efree or 2 * rows * a.cexp >= (BN_FOLD_MIN_BYTES if a.s == 1 else max(BN_FOLD_MIN_BYTES, BN_FOLD_S2_MIN_BYTES)))
             xbwd = expand and not fold and ops.xbwd_rows_ok(rows, a.cexp, a.cin)
+        # stride-2 3x3 blocks whose e is not stored (recompute modes >= 1): the backward forms the e rows from x inside the data-
+        # gradient launch, which is the weight gradient too (ops.dwconv_bwd_data with xw), and folds BatchNorm0: e is not rebuilt
+        efree_s2 = bool(recording and fusable and ops.EFREE_S2 and a.k == 3 and a.s == 2 and self.training and rc >= 1 and fold
+                        and ops.dwconv_bwd_s2_xw_ok(*dw, cin=a.cin, force=ops.EFREE_S2 >= 2))
         return _Plan(n, h, w, oh, ow, self.training, xdw, efree,
                      fp8_expand=bool(expand and self.fp8 and a.cin % 16 == 0 and not ops._rows_ok(rows, a.cexp, a.cin, None, 0)),
                      keep_act=keep_act, fp8_project=keep_act and self.fp8 and a.cexp % 16 == 0 and a.cout > 64,
                      store_e=expand and rc == 0 and not xdw, store_d=rc < 2, store_p=rc < 4,
-                     fuse_proj_dgrad=fuse_proj, fused_dw=fused_dw, fold_bn0=fold, xbwd=xbwd, dw=dw)
+                     fuse_proj_dgrad=fuse_proj, fused_dw=fused_dw, fold_bn0=fold, xbwd=xbwd, dw=dw, efree_s2=efree_s2)
 
     def w_expand(self, transposed=False):
         """cached 16-bit image of the expand conv's weight, [cexp, cin] or transposed.  (Forward, backward and

@@ -736,12 +736,31 @@ template <int K, int CPL, int LP, int NJ, bool EPI = false> struct MarchBwdCfg {
 // stride-1 form above): it writes dZ0 = dA0 * silu'(e*scale + shift) and leaves (sum dZ0, sum dZ0 * xhat0) in stat_partials.
 // The e values of the pixels a block completes are loaded straight into registers with the block's dy prefetch (every
 // lane reads exactly the pixels it writes).
-template <int K, int CPL, int LP, int NJ, bool EPI = false>
+// KS > 0 (3x3, the E-free form of the stride-2 blocks: p.xw set, p.epi_x = the block input x [n,h,w,cin], cin <= 32 * KS): e is
+// not read but FORMED.  The NPIX = RB * 4 * PXW pixels a wave completes in a block are cut into 16-pixel groups; a lane
+// prefetches its 16-byte pieces of x straight into MFMA B-operand fragments (pixel = lane & 15, k group = lane >> 4) beside the
+// block's dy prefetch, and at store time the wave runs D = W_frag . X_frag^T on v_mfma_f32_16x16x32 against the channel tile's
+// expand-weight slice (A-operand fragments resident in LDS, as in conv_lane.hip MODE 4 / 5).  That leaves a lane with 4
+// consecutive channels of ONE pixel, not the marching mapping (a lane = 4 channels of a super-pixel): the raw e values -- rounded
+// once to 16 bits, like the tensor the expand GEMM stores -- pass through a wave-private LDS tile [pixel][channel], from which
+// every lane reads exactly what the e-reading form prefetched.  With p.dw_out the launch is also the conv's WEIGHT gradient:
+// the scatter already meets every (dy value, tap, completed pixel) triple, so a0 = z * sigmoid(z) (the sigmoid silu' needs
+// anyway; rounded to 16 bits like the staged a0 of dwconv_march_bww_kernel) times the dy values of this and the previous row accumulates into K*K per-lane sums, reduced once per workgroup.
+template <int K, int CPL, int LP, int NJ, bool EPI = false, int KS = 0>
 __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dwconv_args p, int strips, int segs, int seg_rows,
                                                                      int ctiles, int gy) {
     using C = MarchBwdCfg<K, CPL, LP, NJ, EPI>;
     typedef typename std::conditional<CPL == 4, uint2, uint32_t>::type ldsv_t;
-    constexpr int SM_BYTES = (EPI && C::BUF_BYTES < 256 * 2 * CPL * 4) ? 256 * 2 * CPL * 4 : C::BUF_BYTES;
+    constexpr bool XW = KS > 0;
+    static_assert(!XW || (EPI && K == 3 && NJ == 1 && CPL == 4), "the e-forming variant is built for the 3x3 epilogue configurations");
+    constexpr int NPIX = C::RB * 4 * C::PXW * NJ;          // pixels a wave completes per block: [dy row][f][px][e]
+    static_assert(!XW || (NPIX % 16 == 0 && C::TCH % 16 == 0), "whole 16 x 16 MFMA tiles");
+    constexpr int NTL = XW ? NPIX / 16 : 1, MT = C::TCH / 16;
+    constexpr int ET_OFF = C::BUF_BYTES, ET_WAVE = NPIX * C::PXB;                 // e tiles [wave][pixel][TCH] behind the dy tile
+    constexpr int AW_OFF = ET_OFF + 4 * ET_WAVE;                                  // A-operand fragments [KS][MT][64 lanes] x 16 bytes
+    constexpr int SM_MIN = (EPI && C::BUF_BYTES < 256 * 2 * CPL * 4) ? 256 * 2 * CPL * 4 : C::BUF_BYTES;
+    constexpr int SM_BYTES = XW ? AW_OFF + KS * MT * 64 * 16 : SM_MIN;
+    static_assert(SM_BYTES >= SM_MIN, "the reductions reuse the tile memory");
     __shared__ __attribute__((aligned(16))) unsigned char smem[SM_BYTES];
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int ct = slot % ctiles, y = (slot / ctiles) * 8 + xcd;
@@ -778,8 +797,34 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
         if (v >= C::RB * C::IW_T * C::VPP) meta[i] = 0xffu;
     }
     f32x2_t acc[C::D][NJ][4][C::H2];                       // [super-row slot][super-column][f*2+e][channel pair]
-    constexpr int NE = EPI ? C::RB * 4 * NJ : 1;           // e pixels a lane completes per block: [dy row][f][i][e]
+    constexpr int NE = (EPI && !XW) ? C::RB * 4 * NJ : 1;  // e pixels a lane completes per block: [dy row][f][i][e]
     ldsv_t enext[NE], ecur[NE];
+    // XW: B-operand fragments of the next block's pixels; the lane's e values in the wave's tile; the weight-gradient sums
+    uint4 xnext[NTL][XW ? KS : 1];
+    unsigned xinb = 0;                                     // bit t: the lane's pixel of group t exists
+    const int xkg = lane >> 4;
+    const int ebase = ET_OFF + wave * ET_WAVE + (lane_ok ? px : 0) * 2 * NJ * C::PXB + lq * (CPL * 2);
+    const bool has_dw = XW && p.dw_out != nullptr;
+    f32x2_t dwa[XW ? K * K : 1][C::H2], inprev[C::NIN][C::H2];
+#pragma unroll
+    for (int t = 0; t < (XW ? K * K : 1); ++t)
+#pragma unroll
+        for (int h = 0; h < C::H2; ++h) dwa[t][h] = f32x2_t{0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < C::NIN; ++i)
+#pragma unroll
+        for (int h = 0; h < C::H2; ++h) inprev[i][h] = f32x2_t{0.f, 0.f};
+    if constexpr (XW) {
+        // fragment (ks, m), lane (i = l & 15, kg = l >> 4) = xw[c0 + m*16 + i][ks*32 + kg*8 .. +8]; zero beyond c / cin
+        uint4* s_w = reinterpret_cast<uint4*>(smem + AW_OFF);
+        for (int idx = tid; idx < KS * MT * 64; idx += 256) {
+            const int l = idx & 63, m = (idx >> 6) % MT, ks = idx / (64 * MT);
+            const int ch = c0 + m * 16 + (l & 15), kk = ks * 32 + (l >> 4) * 8;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (ch < p.c && kk < p.cin) v = *reinterpret_cast<const uint4*>(p.xw + (long long)ch * p.cin + kk);
+            s_w[idx] = v;
+        }
+    }
     f32x2_t e_sc[C::H2], e_sh[C::H2], e_mu[C::H2], ssum[C::H2], ssq[C::H2];
 #pragma unroll
     for (int h = 0; h < C::H2; ++h) {
@@ -805,7 +850,26 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
     unsigned inb = 0, colmask = 0;
     // EPI: e of the pixels the dy rows of block b complete (dy row k of the block completes super-row b*RB + k - (D-1))
     auto epi_load = [&](int img, int j0, int s0, int nrows_i, int b) {
-        if constexpr (EPI) {
+        if constexpr (XW) {
+            // pixel n = ((k * 2 + f) * PXW + px) * 2 + e of the wave's block: dy row k completes super-row b*RB + k - (D-1)
+            const long long ix0 = 2LL * (j0 + wave * C::PXW * NJ) - p.pad_l;
+            xinb = 0;
+#pragma unroll
+            for (int t = 0; t < NTL; ++t) {
+                const int n = t * 16 + (lane & 15);
+                const int k = n / (4 * C::PXW * NJ), f = (n / (2 * C::PXW * NJ)) & 1, pe = n % (2 * C::PXW * NJ);
+                const int sr = b * C::RB + k - (C::D - 1);
+                const long long yy = 2LL * (s0 + sr) - p.pad_t + f, x = ix0 + pe;
+                const bool ok = sr >= 0 && sr < nrows_i && yy >= 0 && yy < p.h && x >= 0 && x < p.w;
+                xinb |= (ok ? 1u : 0u) << t;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const int kk = ks * 32 + xkg * 8;
+                    const bf16_t* a = (ok && kk < p.cin) ? p.epi_x + (((long long)img * p.h + yy) * p.w + x) * p.cin + kk : p.epi_x;
+                    xnext[t][ks] = *reinterpret_cast<const uint4*>(a);                 // unconditional (see stage_load)
+                }
+            }
+        } else if constexpr (EPI) {
             const long long ix = 2LL * (j0 + jl0) - p.pad_l;
 #pragma unroll
             for (int k = 0; k < C::RB; ++k) {
@@ -857,7 +921,29 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
                 *reinterpret_cast<uint4*>(smem + ((meta[i] >> 16) << 4)) = val;
             }
         }
-        if constexpr (EPI) {
+        if constexpr (XW) {
+            const uint4* s_w = reinterpret_cast<const uint4*>(smem + AW_OFF);
+            unsigned char* et = smem + ET_OFF + wave * ET_WAVE + (lane & 15) * C::PXB + xkg * 8;
+#pragma unroll
+            for (int t = 0; t < NTL; ++t) {
+                f32x4_t ea[MT];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) ea[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    uint4 xv = xnext[t][ks];
+                    if (!((xinb >> t) & 1u) || ks * 32 + xkg * 8 >= p.cin) xv = make_uint4(0u, 0u, 0u, 0u);   // (0 * garbage must not be NaN)
+                    const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, xv);
+#pragma unroll
+                    for (int m = 0; m < MT; ++m)
+                        ea[m] = MC_MFMA_16x16x32(__builtin_bit_cast(bf16x8_t, s_w[(ks * MT + m) * 64 + lane]), bfrag, ea[m], 0, 0, 0);
+                }
+                // the lane holds channels m*16 + kg*4 .. +3 of pixel t*16 + (lane & 15): raw e, rounded once
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+                    *reinterpret_cast<uint2*>(et + t * 16 * C::PXB + m * 32) = make_uint2(pack_bf2(ea[m][0], ea[m][1]), pack_bf2(ea[m][2], ea[m][3]));
+            }
+        } else if constexpr (EPI) {
 #pragma unroll
             for (int i = 0; i < NE; ++i) ecur[i] = enext[i];
         }
@@ -894,6 +980,12 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
 #pragma unroll
                         for (int h = 0; h < C::H2; ++h) acc[a][i][q][h] = f32x2_t{0.f, 0.f};
             sr_next = -(C::D - 1);
+            if constexpr (XW) {
+#pragma unroll
+                for (int i = 0; i < C::NIN; ++i)
+#pragma unroll
+                    for (int h = 0; h < C::H2; ++h) inprev[i][h] = f32x2_t{0.f, 0.f};
+            }
             const long long iy = 2LL * (s0 + sr_next) - p.pad_t, ix = 2LL * (j0 + jl0) - p.pad_l;
             optr = reinterpret_cast<bf16_t*>(p.out) + (((long long)img * p.h + iy) * p.w + ix) * p.c + cl;
             ok_mask = 0;
@@ -957,16 +1049,48 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
                                         if ((ok_mask >> (i * 2 + e)) & 1u) {
                                             bf16_t* o = optr + f * row_pitch + (long long)(2 * i + e) * p.c;
                                             uint32_t o2[C::H2];
+                                            [[maybe_unused]] ldsv_t evh = ldsv_t();      // (KS > 0: the pixel's e values, from the wave's tile)
 #pragma unroll
                                             for (int h = 0; h < C::H2; ++h) {
                                                 if constexpr (EPI) {
-                                                    const ldsv_t evv = ecur[(((sb * C::D + jr) * 2 + f) * NJ + i) * 2 + e];
+                                                    ldsv_t evv;
+                                                    if constexpr (XW) {
+                                                        if (h == 0) evh = *reinterpret_cast<const ldsv_t*>(
+                                                            smem + ebase + ((((sb * C::D + jr) * 2 + f) * C::PXW * NJ) * 2 + 2 * i + e) * C::PXB);
+                                                        evv = evh;
+                                                    } else {
+                                                        evv = ecur[(((sb * C::D + jr) * 2 + f) * NJ + i) * 2 + e];
+                                                    }
                                                     uint32_t ew;
                                                     if constexpr (CPL == 4) ew = h == 0 ? evv.x : evv.y; else ew = evv;
                                                     const f32x2_t e2 = {bf_lo(ew), bf_hi(ew)};
                                                     const f32x2_t z = __builtin_elementwise_fma(e2, e_sc[h], e_sh[h]);
                                                     const f32x2_t a2 = acc[sl][i][f * 2 + e][h];
-                                                    const f32x2_t dz2 = a2 * silu_grad2_f(z);
+                                                    f32x2_t dz2;
+                                                    if constexpr (XW) {
+                                                        // ONE sigmoid per element: silu' (the expression of silu_grad2_f) and a0 = z * s
+                                                        const f32x2_t s = sigmoid2_f(z);
+                                                        dz2 = a2 * (s * __builtin_elementwise_fma(z, f32x2_t{1.f, 1.f} - s, f32x2_t{1.f, 1.f}));
+                                                        if (has_dw) {
+                                                            // dW[f+2d, e+2d'] += dy[o'-d, j-d'] * a0[pixel]: this row (d = 0), the one before (d = 1)
+                                                            // (a0 rounded to 16 bits: the value the forward's stencil and the separate
+                                                            // weight-gradient launch read from their staged tiles)
+                                                            const uint32_t a0b = pack_bf2(z.x * s.x, z.y * s.y);
+                                                            const f32x2_t a0 = {bf_lo(a0b), bf_hi(a0b)};
+#pragma unroll
+                                                            for (int d = 0; d < C::D; ++d) {
+                                                                if (f + 2 * d >= K) continue;
+#pragma unroll
+                                                                for (int dd = 0; dd < C::D; ++dd) {
+                                                                    if (e + 2 * dd >= K) continue;
+                                                                    const f32x2_t g = d == 0 ? in[C::D - 1 + i - dd][h] : inprev[C::D - 1 + i - dd][h];
+                                                                    dwa[(f + 2 * d) * K + e + 2 * dd][h] = __builtin_elementwise_fma(g, a0, dwa[(f + 2 * d) * K + e + 2 * dd][h]);
+                                                                }
+                                                            }
+                                                        }
+                                                    } else {
+                                                        dz2 = a2 * silu_grad2_f(z);
+                                                    }
                                                     o2[h] = pack_bf2(dz2.x, dz2.y);
                                                     const f32x2_t r = {bf_lo(o2[h]), bf_hi(o2[h])};     // reductions of the stored (rounded) dZ0
                                                     ssum[h] += r;
@@ -990,6 +1114,12 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
                         for (int q = 0; q < 4; ++q)
 #pragma unroll
                             for (int h = 0; h < C::H2; ++h) acc[sl][i][q][h] = f32x2_t{0.f, 0.f};
+                    if constexpr (XW) {
+#pragma unroll
+                        for (int i = 0; i < C::NIN; ++i)
+#pragma unroll
+                            for (int h = 0; h < C::H2; ++h) inprev[i][h] = in[i][h];
+                    }
                 }
             }
         }
@@ -1016,6 +1146,29 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
                 p.stat_partials[((long long)y * 2 + which) * p.c + c0 + ch] = sv;
             }
         }
+        if constexpr (XW) {
+            if (has_dw) {      // as dwconv_march_bww_kernel: one LDS reduction + one atomic per (tap, channel) per workgroup
+                for (int t = 0; t < K * K; ++t) {
+                    __syncthreads();
+#pragma unroll
+                    for (int h = 0; h < C::H2; ++h) {
+                        f32x2_t a = f32x2_t{0.f, 0.f};
+#pragma unroll
+                        for (int tt = 0; tt < K * K; ++tt)
+                            if (tt == t) a = dwa[tt][h];              // static register indexing
+                        red[tid * CPL + 2 * h] = a.x;
+                        red[tid * CPL + 2 * h + 1] = a.y;
+                    }
+                    __syncthreads();
+                    if (tid < C::TCH && c0 + tid < p.c) {
+                        float sv = 0.f;
+                        for (int wv = 0; wv < 4; ++wv)
+                            for (int q = 0; q < C::PXW; ++q) sv += red[(wv * 64 + q * LP + tid / CPL) * CPL + tid % CPL];
+                        atomicAdd(p.dw_out + (long long)t * p.c + c0 + tid, sv);
+                    }
+                }
+            }
+        }
     }
 }
 
@@ -1038,11 +1191,11 @@ template <int K, int CPL, int LP, int NJ, bool EPI = false> int march_bwd_s2_pla
     *strips_ = strips; *segs_ = segs; *seg_rows_ = seg_rows; *ctiles_ = ctiles;
     return (int)((nitems + per - 1) / per);
 }
-template <int K, int CPL, int LP, int NJ> int launch_march_bwd_s2_epi(const mc_dwconv_args& p, hipStream_t st) {
+template <int K, int CPL, int LP, int NJ, int KS = 0> int launch_march_bwd_s2_epi(const mc_dwconv_args& p, hipStream_t st) {
     int strips, segs, seg_rows, ctiles;
     const int gy = march_bwd_s2_plan<K, CPL, LP, NJ, true>(p, &strips, &segs, &seg_rows, &ctiles);
     const int gy8 = (gy + 7) / 8 * 8;
-    hipLaunchKernelGGL((dwconv_march_bwd_s2_kernel<K, CPL, LP, NJ, true>), dim3(gy8 * ctiles), dim3(256), 0, st, p, strips, segs,
+    hipLaunchKernelGGL((dwconv_march_bwd_s2_kernel<K, CPL, LP, NJ, true, KS>), dim3(gy8 * ctiles), dim3(256), 0, st, p, strips, segs,
                        seg_rows, ctiles, gy);
     MC_LAUNCH_CHECK();
     return MC_OK;
@@ -1227,16 +1380,37 @@ extern "C" int mc_dwconv_stat_rows(const mc_dwconv_args* a) {
     return a->stride == 1 ? march_rows<5, 1>(*a) : march_rows<5, 2>(*a);
 }
 
-// rows of stat_partials written by mc_dwconv_bwd_data with the stride-2 BatchNorm-backward epilogue (epi_x set)
-extern "C" int mc_dwconv_bwd_data_stat_rows(const mc_dwconv_args* a) {
+// the work split of mc_dwconv_bwd_data with the stride-2 BatchNorm-backward epilogue (epi_x set; the same with and without xw):
+// plan[4] = column strips per row, row segments per image, super-rows per segment, channel tiles; returns the persistent
+// workgroups per channel tile = the rows of stat_partials
+extern "C" int mc_dwconv_bwd_data_plan(const mc_dwconv_args* a, int* plan) {
     const mc_dwconv_args& p = *a;
-    int s1, s2, s3, s4;
     if (p.stride != 2) return 0;
     if (p.k == 3) {
-        if (p.c % 48 == 0 && p.c < 192) return march_bwd_s2_plan<3, 4, 12, 1, true>(p, &s1, &s2, &s3, &s4);
-        return march_bwd_s2_plan<3, 4, 16, 1, true>(p, &s1, &s2, &s3, &s4);
+        if (p.c % 48 == 0 && p.c < 192) return march_bwd_s2_plan<3, 4, 12, 1, true>(p, plan, plan + 1, plan + 2, plan + 3);
+        return march_bwd_s2_plan<3, 4, 16, 1, true>(p, plan, plan + 1, plan + 2, plan + 3);
     }
-    return march_bwd_s2_plan<5, 2, 32, 2, true>(p, &s1, &s2, &s3, &s4);
+    return march_bwd_s2_plan<5, 2, 32, 2, true>(p, plan, plan + 1, plan + 2, plan + 3);
+}
+// rows of stat_partials written by mc_dwconv_bwd_data with the stride-2 BatchNorm-backward epilogue (epi_x set)
+extern "C" int mc_dwconv_bwd_data_stat_rows(const mc_dwconv_args* a) {
+    int plan[4];
+    return mc_dwconv_bwd_data_plan(a, plan);
+}
+
+// The E-free form of mc_dwconv_bwd_data (args->xw set: epi_x is the block input x [n,h,w,cin], e = x . xw^T is formed in the
+// launch; dw_out: the conv's weight gradient from the same launch): 3x3, stride 2, c % 8 == 0, cin % 8 == 0, cin <= 64
+extern "C" int mc_dwconv_bwd_data_xw_supported(const mc_dwconv_args* a) {
+    return a->k == 3 && a->stride == 2 && a->xw && a->epi_x && a->c > 0 && a->c % 8 == 0 && a->cin > 0 && a->cin % 8 == 0 && a->cin <= 64;
+}
+// ... and the shapes on which it measured faster than the three launches it replaces (expand GEMM rebuild + weight gradient +
+// e-reading data gradient; profiles/dw_s2_efree_ab.md)
+extern "C" int mc_dwconv_bwd_data_xw_preferred(const mc_dwconv_args* a) {
+    if (!mc_dwconv_bwd_data_xw_supported(a)) return 0;
+    // measured at 32 images (scripts/dw_s2_efree_ab.py): 24 -> 144 at 760 x 456 (1.6 G expanded elements) 4.3 -> 1.95 ms, 64 -> 384 at
+    // 190 x 114 (0.27 G) 0.61 -> 0.44 ms.  The gain is the expanded tensor's traffic: smaller tensors (the launch-bound
+    // configurations) and expansions below 4 were not measured and stay on the three launches.
+    return a->c >= 4 * a->cin && (long long)a->n * a->h * a->w * a->c >= 200000000LL;
 }
 
 extern "C" int mc_dwconv_fwd(const mc_dwconv_args* a, void* stream) {
@@ -1263,6 +1437,18 @@ extern "C" int mc_dwconv_bwd_data(const mc_dwconv_args* a, void* stream) {
     MC_CHECK(p.dy && p.w_kkc, "dwconv_bwd_data: null dy / w");
     MC_CHECK(!p.epi_x || (p.stride == 2 && p.epi_scale && p.epi_shift && p.epi_mean && p.epi_invstd && p.stat_partials),
              "dwconv_bwd_data: the BatchNorm-backward epilogue is provided for stride 2 here (stride 1: mc_dwconv_fwd on flipped taps) and needs scale/shift/mean/invstd and stat_partials");
+    MC_CHECK(!p.xw || mc_dwconv_bwd_data_xw_supported(a),
+             "dwconv_bwd_data (e from the block input): 3x3 stride-2 conv with the epilogue operands, cin % 8 == 0, cin <= 64");
+    MC_CHECK(!p.dw_out || p.xw, "dwconv_bwd_data: the fused weight gradient (dw_out) is provided for the e-forming form (xw)");
+    MC_CHECK(!(p.epi_x && p.stat_rows > 0) || p.stat_rows == mc_dwconv_bwd_data_stat_rows(a),
+             "dwconv_bwd_data: stat_partials was sized for another configuration");
+    if (p.xw) {
+        hipStream_t st = (hipStream_t)stream;
+        MC_CHECK(mc_aligned16(p.epi_x) && mc_aligned16(p.xw), "dwconv_bwd_data (e from the block input): x / xw must be 16-byte aligned");
+        const bool t48 = p.c % 48 == 0 && p.c < 192;
+        if (p.cin <= 32) return t48 ? launch_march_bwd_s2_epi<3, 4, 12, 1, 1>(p, st) : launch_march_bwd_s2_epi<3, 4, 16, 1, 1>(p, st);
+        return t48 ? launch_march_bwd_s2_epi<3, 4, 12, 1, 2>(p, st) : launch_march_bwd_s2_epi<3, 4, 16, 1, 2>(p, st);
+    }
     if (p.stride == 2 && p.epi_x) {
         hipStream_t st = (hipStream_t)stream;
         if (p.k == 3) {

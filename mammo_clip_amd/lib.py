@@ -134,6 +134,9 @@ _SIGS = {
     "mc_dwconv_bwd_data_stat_rows": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_fwd": ([C.POINTER(DwconvArgs), P], I),
     "mc_dwconv_bwd_data": ([C.POINTER(DwconvArgs), P], I),
+    "mc_dwconv_bwd_data_xw_supported": ([C.POINTER(DwconvArgs)], I),
+    "mc_dwconv_bwd_data_plan": ([C.POINTER(DwconvArgs), C.POINTER(C.c_int)], I),
+    "mc_dwconv_bwd_data_xw_preferred": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_weight": ([C.POINTER(DwconvArgs), P], I),
     "mc_dwconv_set_lane_mode": ([I], I),
     "mc_dwconv_lane_supported": ([C.POINTER(DwconvArgs)], I),

@@ -654,13 +654,37 @@ def _dwconv_fwd_impl(x, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, pro=
     return (y, part) if stats else y
 
 
-def _dwconv_bwd_data_impl(dy, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, w_kkc_flipped=None, epi=None):
+def _dwconv_bwd_data_impl(dy, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, w_kkc_flipped=None, epi=None, xw=None, dw=False):
     """dx [n*h*w, c].  stride 1 runs the LDS-tiled forward kernel on the flipped filter; stride 2 the marching
     super-pixel kernel.  epi = (e, BNStats): the launch finishes the BatchNorm + SiLU backward of the conv's input
-    silu(bn(e)) and returns (dZ, BatchNorm-backward partials) instead of dx, see dwconv_fwd."""
+    silu(bn(e)) and returns (dZ, BatchNorm-backward partials) instead of dx, see dwconv_fwd.
+    xw = (x, we) (3x3 stride 2, epi = (None, BNStats)): the e rows are formed from the block input x [n*h*w, cin] and the expand
+    weight we [c, cin] inside the launch -- e is not read (and need not exist); dw=True: the same launch is the conv's weight
+    gradient too: returns (dZ, partials, dW [k*k, c] f32 in the conv's own tap order)."""
     if stride == 1 and w_kkc_flipped is not None:
+        assert xw is None and not dw
         return _dwconv_fwd_impl(dy, w_kkc_flipped, n, oh, ow, c, k, 1, k - 1 - pad_l, k - 1 - pad_t, h, w, epi=epi)
     assert epi is None or stride == 2
+    if xw is not None:
+        x, we = xw
+        assert epi is not None and x.is_contiguous() and we.is_contiguous() and we.shape == (c, x.shape[1]) and x.shape[0] == n * h * w
+        cin, st = x.shape[1], epi[1]
+        a = _dw_args(n, h, w, c, k, stride, pad_l, pad_t, oh, ow)
+        dz = empty((n * h * w, c), BF16, dy)
+        a.dy, a.out, a.w_kkc = _p(dy), _p(dz), _p(w_kkc)
+        a.epi_x, a.epi_scale, a.epi_shift, a.epi_mean, a.epi_invstd = _p(x), _p(st.scale), _p(st.shift), _p(st.mean), _p(st.invstd)
+        a.xw, a.cin = _p(we), cin
+        rows = L.load().mc_dwconv_bwd_data_stat_rows(C.byref(a))
+        part = empty((rows, 2, c), torch.float32, dy)
+        a.stat_partials, a.stat_rows = _p(part), rows
+        dwdw = None
+        if dw:
+            dwdw = torch.zeros((k * k, c), dtype=torch.float32, device=dy.device)
+            a.dw_out = _p(dwdw)
+        _note(2 * n * (c * (oh * ow + h * w) + cin * h * w), (4 if dw else 2) * n * c * oh * ow * k * k + 2 * n * h * w * c * cin)
+        L.call("mc_dwconv_bwd_data", C.byref(a), _st(), kind=f"k{k}s{stride}|dgrad_bn|x")
+        return (dz, part, dwdw) if dw else (dz, part)
+    assert not dw
     a = _dw_args(n, h, w, c, k, stride, pad_l, pad_t, oh, ow)
     dx = empty((n * h * w, c), BF16, dy)
     a.dy, a.out, a.w_kkc = _p(dy), _p(dx), _p(w_kkc)
@@ -707,6 +731,27 @@ def dwconv_bwd_fused_ok(n, h, w, c, k, stride, pad_l, pad_t, oh, ow, force=False
             a.xw, a.cin = 16, cin
         lib_ = L.load()
         hit = _FUSED_OK[key] = bool(lib_.mc_dwconv_bwd_fused_supported(C.byref(a)) if force else lib_.mc_dwconv_bwd_fused_preferred(C.byref(a)))
+    return hit
+
+
+# stride-2 3x3 blocks whose backward neither rebuilds nor reads the expanded tensor (mc_dwconv_bwd_data with xw + dw_out, then the
+# folded BatchNorm0 backward), in the recompute modes that do not store e; 0 = off (A/B), 1 = where the library prefers the
+# launch, 2 = wherever it is supported (tests at small sizes)
+EFREE_S2 = int(os.environ.get("MC_EFREE_S2", "1"))
+_S2_XW_OK = {}
+
+
+def dwconv_bwd_s2_xw_ok(n, h, w, c, k, stride, pad_l, pad_t, oh, ow, cin, force=False):
+    """does the E-free stride-2 data gradient (mc_dwconv_bwd_data with xw) take / win this conv?  (geometry only; cached)"""
+    if stride != 2 or k != 3:
+        return False
+    key = (n, h, w, c, k, pad_l, pad_t, oh, ow, cin, force)
+    hit = _S2_XW_OK.get(key)
+    if hit is None:
+        a = _dw_args(n, h, w, c, k, stride, pad_l, pad_t, oh, ow)
+        a.epi_x, a.xw, a.cin = 16, 16, cin              # any non-null value: only looked at
+        lib_ = L.load()
+        hit = _S2_XW_OK[key] = bool(lib_.mc_dwconv_bwd_data_xw_supported(C.byref(a)) if force else lib_.mc_dwconv_bwd_data_xw_preferred(C.byref(a)))
     return hit
 
 
@@ -1435,10 +1480,11 @@ def dwconv_fwd(x, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, pro=None, 
     return (y, part) if stats else y
 
 
-def dwconv_bwd_data(dy, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, w_kkc_flipped=None, epi=None):
+def dwconv_bwd_data(dy, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, w_kkc_flipped=None, epi=None, xw=None, dw=False):
     if epi is not None or not dy.is_cuda:
-        _chk_dev(dy, w_kkc)
-        return _dwconv_bwd_data_impl(dy, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, w_kkc_flipped, epi)
+        _chk_dev(dy, w_kkc, *(xw or ()))
+        return _dwconv_bwd_data_impl(dy, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, w_kkc_flipped, epi, xw, dw)
+    assert xw is None and not dw
     return _OP_DWCONV_DGRAD(dy, w_kkc, n, h, w, k, stride, pad_l, pad_t, oh, ow, w_kkc_flipped)
 
 
