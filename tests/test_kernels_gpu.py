@@ -4,6 +4,15 @@ same op, on seeded inputs.  GPU only (`pytest -m gpu`).
 Tolerances: kernels compute in fp32 from bf16 operands and round the result once to bf16, so the bound is
 bf16 round-off: max-abs error <= 1e-2 * max|ref| (2^-8 = 3.9e-3 per rounding) unless noted; fp32-in/fp32-out
 kernels are held to 1e-4.
+
+Launchers with a capped grid (the row, element, cast and column-sum kernels) run their later passes only past a
+row / element count; the `*_past_the_grid_cap` tests cross each cap by one ragged workgroup, with fp64 references:
+    per-row / per-element output   check_late(): `check` on the whole tensor AND on the slice past the first pass,
+                                   so the later passes are normalised by their own max|ref|
+    sums over rows (dgamma, ...)   a second call whose input is zero in the rows of the first pass: the sum then comes
+                                   from the later passes alone and is compared with the fp64 sum of those rows
+max|ref| of the whole tensor is not enough for a capped reduction: a sum over 2053 rows that lost its last 5 rows moves
+by ~1.6 % of max|ref| and, with more rows, falls under any bound that a complete sum is held to.
 """
 import math
 import os
@@ -568,8 +577,9 @@ def test_misc_cast_transpose_colsum_dropout():
 
 
 # ------------------------------------------------------------------------------------------------ BERT pieces
-def test_bert_embed_fwd_bwd():
-    b, t, h, vocab = 3, 16, 64, 50
+@pytest.mark.parametrize("h", [64, 520])       # 520: 65 vectors, one lane in the second vector of the row
+def test_bert_embed_fwd_bwd(h):
+    b, t, vocab = 3, 16, 50
     g = torch.Generator().manual_seed(58)
     ids = torch.randint(0, vocab, (b, t), generator=g).to(DEV)
     tt = torch.zeros_like(ids)
@@ -592,7 +602,9 @@ def test_bert_embed_fwd_bwd():
         check(got, refg, 2e-3, "embed " + nm)
 
 
-@pytest.mark.parametrize("rows,h", [(37, 64), (300, 768)])
+@pytest.mark.parametrize("rows,h", [(37, 64), (300, 768),
+                                    # vectors of 8 per lane: one vector in all, 63, exactly 64 (every lane once), 65, the limit 128
+                                    (37, 8), (37, 504), (37, 512), (37, 520), (37, 1024)])
 def test_add_ln_fwd_bwd(rows, h):
     x, res = rnd(rows, h, seed=65), rnd(rows, h, seed=66)
     gamma = (rnd(h, seed=67, dtype=torch.float32) * 0.1 + 1).requires_grad_(True)
@@ -1851,3 +1863,383 @@ def test_fused_launches_random_geometry_screen():
     script = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "xdw_fuzz.py")
     r = subprocess.run([sys.executable, script, "150", "7"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ------------------------------------------------------------------------------------------------ past the grid caps
+# Each shape is the smallest that leaves the first pass of its launcher's capped grid by one ragged workgroup (the caps are
+# in the launchers of bert.hip / util.hip); references are fp64 torch on the 16-bit-rounded inputs the kernel reads.  Every
+# op is called once per distinct input: the wrappers allocate their outputs, and a block handed back by the caching
+# allocator could still hold an earlier, correct answer.
+def check_late(got, ref, first, tol, what=""):
+    """`check` on the whole tensor and on the part past the first pass (dim 0: rows, or the elements of a flat view), which
+    is then normalised by its own max|ref|"""
+    check(got, ref, tol, what)
+    assert got.shape[0] > first, (what, got.shape, first)
+    check(got[first:], ref[first:], tol, f"{what} [{first}:]")
+
+
+def _add_ln_ref64(x, res, gamma, beta, dys):
+    """fp64 LayerNorm(x + res) and, per upstream gradient in dys, the gradients of (x, res, gamma, beta)"""
+    leaves = [v.double().requires_grad_(True) for v in (x, res, gamma, beta)]
+    y = F.layer_norm(leaves[0] + leaves[1], (x.shape[1],), leaves[2], leaves[3], 1e-12)
+    return y.detach(), [torch.autograd.grad(y, leaves, dy.double(), retain_graph=True) for dy in dys]
+
+
+def test_add_ln_past_the_grid_cap():
+    """forward: 2048 workgroups x 4 rows, 8197 rows = one 5-row second pass; backward: 512 workgroups x 4 rows, 4101 rows =
+    three passes.  dgamma / dbeta of the later passes alone: dy zero in the rows of the first backward pass."""
+    h, FWD, BWD = 768, 8192, 2048
+    x, res = rnd(FWD + 5, h, seed=600), rnd(FWD + 5, h, seed=601)
+    gamma, beta = rnd(h, seed=602, dtype=torch.float32) * 0.1 + 1, rnd(h, seed=603, dtype=torch.float32) * 0.1
+    ref, _ = _add_ln_ref64(x, res, gamma, beta, [])
+    y, mean, rstd = ops.add_ln_fwd(x, res, gamma, beta, 1e-12, 0.0, 1, 0)
+    check_late(y, ref, FWD, 1e-2, "add_ln fwd")
+    s = x.double() + res.double()
+    check_late(mean, s.mean(1), FWD, 1e-4, "add_ln mean")
+    check_late(rstd, (s.var(1, unbiased=False) + 1e-12).rsqrt(), FWD, 1e-4, "add_ln rstd")
+    rows = 2 * BWD + 5
+    xb, rb, mb, sb = x[:rows], res[:rows], mean[:rows], rstd[:rows]     # (per-row statistics: checked above)
+    dy = rnd(rows, h, seed=604)
+    dy0 = dy.clone()
+    dy0[:BWD] = 0
+    _, (g, g0) = _add_ln_ref64(xb, rb, gamma, beta, [dy, dy0])
+    dx, dres, dgamma, dbeta = ops.add_ln_bwd(dy, xb, rb, gamma, mb, sb, 0.0, 1, 0)
+    check_late(dx, g[0], BWD, 1.5e-2, "add_ln dx")
+    check_late(dres, g[1], BWD, 1.5e-2, "add_ln dres")
+    check(dgamma, g[2], 2e-3, "add_ln dgamma")
+    check(dbeta, g[3], 2e-3, "add_ln dbeta")
+    dx0, dres0, dgamma0, dbeta0 = ops.add_ln_bwd(dy0, xb, rb, gamma, mb, sb, 0.0, 1, 0)
+    check(dgamma0, g0[2], 2e-3, "add_ln dgamma of passes two and three")
+    check(dbeta0, g0[3], 2e-3, "add_ln dbeta of passes two and three")
+    assert float(dx0[:BWD].float().abs().max()) == 0.0 and float(dres0[:BWD].float().abs().max()) == 0.0
+    check(dx0[BWD:], g0[0][BWD:], 1.5e-2, "add_ln dx of passes two and three")
+    check(dres0[BWD:], g0[1][BWD:], 1.5e-2, "add_ln dres of passes two and three")
+
+
+def test_add_ln_dropout_past_the_grid_cap():
+    """p = 0.1 at 8197 rows: the forward is bit-reproducible, and the mask the backward regenerates is the forward's, in the
+    later passes of both (forward rows >= 8192, backward rows >= 2048)"""
+    rows, h, p, FWD, BWD = 8197, 768, 0.1, 8192, 2048
+    x, res = rnd(rows, h, seed=605), torch.zeros(rows, h, device=DEV, dtype=BF)
+    gamma, beta = torch.ones(h, device=DEV), torch.zeros(h, device=DEV)
+    y1, m1, r1 = ops.add_ln_fwd(x, res, gamma, beta, 1e-12, p, 77, 5)
+    y2, _, _ = ops.add_ln_fwd(x, res, gamma, beta, 1e-12, p, 77, 5)           # (y1 is alive: y2 is another block)
+    assert torch.equal(y1, y2)
+    # forward mask: with res = 0, gamma = 1, beta = 0 the normalised row gives the dropped-out sum back, s = y / rstd + mean,
+    # which is 0 where x was dropped and x / 0.9 where it was kept.  y carries one 16-bit rounding (<= 2^-9 |y|, |y| < 6,
+    # 1 / rstd ~ 1), so s is known to 0.02: looked at where |x| > 0.25, kept is |s| > 0.27 - 0.02 and dropped is |s| < 0.02
+    s = y1.float() / r1[:, None] + m1[:, None]
+    bigx = x.float().abs() > 0.25
+    keep_f = s.abs() > 0.12
+    frac = float(keep_f[FWD:][bigx[FWD:]].float().mean())
+    assert abs(frac - 0.9) < 0.02, frac
+    dy = rnd(rows, h, seed=606)
+    dx, dres, _, _ = ops.add_ln_bwd(dy, x, res, gamma, m1, r1, p, 77, 5)
+    big = dres.float().abs() > 1e-3
+    keep_b = dx.float().abs() > 0
+    both = bigx & big
+    assert torch.equal(keep_b[both], keep_f[both])
+    assert int(both[FWD:].sum()) > 1000 and torch.equal(keep_b[FWD:][both[FWD:]], keep_f[FWD:][both[FWD:]])
+    # the ratio check of test_add_ln_dropout_consistency on the rows of the later backward passes
+    dxl, dresl, bigl = dx[BWD:].float(), dres[BWD:].float(), big[BWD:]
+    sel = (dxl.abs() > 0) & bigl
+    frac = float(sel.float().sum() / bigl.float().sum())
+    assert abs(frac - 0.9) < 0.02, frac
+    ratio = dxl[sel] / dresl[sel]
+    assert float((ratio - 1 / 0.9).abs().max()) < 2e-2
+
+
+def test_bert_embed_past_the_grid_cap():
+    """33 x 249 = 8217 rows: a 25-row second forward pass; backward: 2048 / 249 = 8 batch rows per round, five rounds with
+    one batch row in the last.  97 words: every word row collects ~85 atomic adds.  Second backward call: dy zero in batch
+    rows < 8, so all five gradients come from rounds two to five alone."""
+    b, t, h, vocab, FWD = 33, 249, 64, 97, 8192
+    g = torch.Generator().manual_seed(610)
+    ids = torch.randint(0, vocab, (b, t), generator=g).to(DEV)
+    tt = torch.randint(0, 2, (b, t), generator=g).to(DEV)
+    word, pos, typ = (rnd(n, h, seed=611 + i, dtype=torch.float32) for i, n in enumerate((vocab, 256, 2)))
+    gamma, beta = rnd(h, seed=614, dtype=torch.float32) * 0.1 + 1, rnd(h, seed=615, dtype=torch.float32) * 0.1
+    lv = [v.double().requires_grad_(True) for v in (word, pos, typ, gamma, beta)]
+    ref = F.layer_norm(lv[0][ids] + lv[1][:t][None] + lv[2][tt], (h,), lv[3], lv[4], 1e-12)
+    y, mean, rstd = ops.bert_embed_fwd(ids, tt, word, pos, typ, gamma, beta, 1e-12, 0.0, 1, 0)
+    check_late(y, ref.detach().view(b * t, h), FWD, 1e-2, "embed fwd")
+    dy = rnd(b * t, h, seed=616)
+    dy0 = dy.clone()
+    dy0[:8 * t] = 0
+    for d, tag in ((dy, ""), (dy0, " of rounds two to five")):
+        refs = torch.autograd.grad(ref, lv, d.double().view(b, t, h), retain_graph=True)
+        got = ops.bert_embed_bwd(d, ids, tt, word, pos, typ, gamma, mean, rstd, 0.0, 1, 0)
+        for a, r, nm in zip(got, refs, ("dword", "dpos", "dtype", "dgamma", "dbeta")):
+            check(a, r, 2e-3, "embed " + nm + tag)
+
+
+def test_gelu_past_the_grid_cap():
+    """8192 workgroups x 256 lanes x 8 elements = 16,777,216 elements; 5464 x 3072 leaves 1024 vectors to a second pass"""
+    rows, c, first = 5464, 3072, 8192 * 256 * 8
+    x, dy = rnd(rows, c, seed=620), rnd(rows, c, seed=621)
+    chunk = 683                                                  # fp64 in 8 pieces, kept as fp32 (2^-24: nothing beside 1e-2)
+    ref = torch.cat([F.gelu(xc.double()).float() for xc in x.split(chunk)])
+    check_late(ops.gelu_fwd(x).view(-1), ref.view(-1), first, 1e-2, "gelu")
+    del ref
+
+    def dgelu(xc):                                               # d/dx [x Phi(x)] = Phi(x) + x phi(x)
+        xd = xc.double()
+        return 0.5 * (1 + torch.erf(xd / math.sqrt(2))) + xd * torch.exp(-0.5 * xd * xd) / math.sqrt(2 * math.pi)
+    refd = torch.cat([(dc.double() * dgelu(xc)).float() for xc, dc in zip(x.split(chunk), dy.split(chunk))])
+    check_late(ops.gelu_bwd(dy, x).view(-1), refd.view(-1), first, 1e-2, "gelu bwd")
+
+
+@pytest.mark.parametrize("rows,t,first", [(32771, 256, 32768),     # 8 keys per lane, 32 lanes per row: 4096 workgroups x 8 rows
+                                          (16389, 40, 16384)])     # one key per lane-slot: 4096 workgroups x 4 rows
+def test_softmax_past_the_grid_cap(rows, t, first):
+    """test_softmax_fwd_bwd's masking, checks and bounds, one ragged workgroup past the first pass, against fp64"""
+    live = (t * 3) // 4
+    s = rnd(rows, t, seed=630, dtype=torch.float32) * 3
+    s[:, live:] = -3.0e38
+    sr = s.double().requires_grad_(True)
+    ref = torch.softmax(sr, -1)
+    probs, pd = ops.softmax_fwd(s, 0.0, 1, 0)
+    assert pd.data_ptr() == probs.data_ptr()
+    check_late(probs, ref.detach(), first, 1e-2, "softmax")
+    dp = rnd(rows, t, seed=631, dtype=torch.float32)
+    dpd = dp.double()
+    ref.backward(dpd)
+    refds = sr.grad * 0.125
+    pq = ref.detach().float().to(BF)                             # the 16-bit probabilities the kernel sees
+    pb = pq.double()
+    refds2 = pb * (dpd - (pb * dpd).sum(-1, keepdim=True)) * 0.125
+    ds = ops.softmax_bwd(pq, dp, 0.0, 1, 0, 0.125)
+    check_late(ds, refds2, first, 1e-2, "softmax bwd")
+    assert relerr(ds, refds) < 5e-2 and relerr(ds[first:], refds[first:]) < 5e-2
+    if t % 8:
+        return                                                   # dropout draws are per 8-element group
+    probs2, pd2 = ops.softmax_fwd(s, 0.1, 5, 2)
+    check_late(probs2, ref.detach(), first, 1e-2, "softmax (dropout call)")
+    on = probs2[:, :live].float() > 0
+    nz = float((pd2[:, :live].float() > 0)[on].float().mean())
+    assert abs(nz - 0.9) < 0.03, nz
+    # mask regeneration in the backward, evaluated on the rows past the first pass (and on all of them)
+    keep = (pd2.double() > 0).double() / 0.9
+    pb2 = probs2.double()
+    refds3 = pb2 * (dpd * keep - (pb2 * dpd * keep).sum(-1, keepdim=True)) * 0.125
+    ds3 = ops.softmax_bwd(probs2, dp, 0.1, 5, 2, 0.125)
+    sel = pb2 > 1e-3                                             # where a dropped probability is distinguishable from 0
+    err = (ds3.double() - refds3).abs()
+    assert int(sel[first:].sum()) > 50
+    assert float(err[first:][sel[first:]].max()) <= 2e-2 * float(refds3[first:].abs().max()) + 1e-3
+    assert float(err[sel].max()) <= 2e-2 * float(refds3.abs().max()) + 1e-3
+
+
+def test_casts_past_the_grid_cap_and_tails():
+    """bit-exact against torch: cast_f32_bf16 (4096 workgroups x 2048 elements, then 2048 + 5: a second pass that ends in the
+    scalar tail), the low-part cast and the widening cast (8192 x 256 elements, then 300), misaligned source, transpose"""
+    x = rnd(4096 * 2048 + 2048 + 5, seed=640, dtype=torch.float32)
+    assert torch.equal(ops.cast_bf16(x), x.to(BF))
+    # a source at element offset 1 (4 bytes past a 16-byte boundary).  The wrapper's .contiguous() returns a 1-D slice as it
+    # is, so the kernel does see the misaligned pointer and takes the scalar branch for both groups; n = 13 also ends in a
+    # 5-element tail.  out= : no cached image
+    base = rnd(16, seed=641, dtype=torch.float32)
+    src = base[1:14]
+    assert src.data_ptr() % 16 == 4
+    out = torch.full((16,), 7.0, device=DEV, dtype=BF)
+    ops.cast_bf16(src, out=out[:13])
+    assert torch.equal(out[:13], src.to(BF)) and bool((out[13:].float() == 7.0).all())
+    al = rnd(13, seed=642, dtype=torch.float32)                  # aligned: one vector, then the tail
+    out = torch.full((16,), 7.0, device=DEV, dtype=BF)
+    ops.cast_bf16(al, out=out[:13])
+    assert torch.equal(out[:13], al.to(BF)) and bool((out[13:].float() == 7.0).all())
+    x2 = rnd(8192 * 256 + 300, seed=643, dtype=torch.float32)
+    hi = x2.to(BF)
+    assert torch.equal(ops.cast_bf16_lo(x2), (x2 - hi.float()).to(BF))
+    assert torch.equal(ops.cast_f32(hi), hi.float())
+    m = rnd(70, 45, seed=644, dtype=torch.float32)               # 3 x 2 tiles of 32, ragged in both directions
+    assert torch.equal(ops.cast_transpose_bf16(m), m.t().contiguous().to(BF))
+    v = rnd(1000, seed=645, dtype=torch.float32)
+    sd = torch.tensor([1.7], device=DEV)
+    check(ops.scale_f32(v, alpha=0.5), v * 0.5, 1e-6, "scale_f32")
+    check(ops.scale_f32(v, sd, 0.5), v * (torch.tensor(0.5, device=DEV) * sd), 1e-6, "scale_f32 scalar_dev")
+
+
+def test_colsum_past_the_grid_cap():
+    """c = 2048: one row per workgroup iteration, 16 rows per workgroup -> 513 workgroups capped at 512, so rows >= 8192 are a
+    second pass.  Sums of the last / first eighth of the rows alone; accumulate into out=; row stride != c."""
+    m, c = 8200, 2048
+    assert L.load().mc_colsum_rows(m, c) == 512 and 512 * 16 < m
+    x = rnd(m, c, seed=650)
+    check(ops.colsum(x), x.double().sum(0), 1e-4, "colsum")
+    late = x.clone()
+    late[:m - m // 8] = 0
+    check(ops.colsum(late), late.double().sum(0), 1e-4, "colsum, last eighth of the rows")
+    early = x.clone()
+    early[m // 8:] = 0
+    check(ops.colsum(early), early.double().sum(0), 1e-4, "colsum, first eighth of the rows")
+    out0 = rnd(c, seed=651, dtype=torch.float32) * 50
+    out = out0.clone()
+    assert ops.colsum(late, out=out, accumulate=True) is out
+    check(out, out0.double() + late.double().sum(0), 1e-4, "colsum accumulate")
+    w = rnd(m, 256, seed=652)
+    check(ops.colsum(w[:, :240]), w[:, :240].double().sum(0), 1e-4, "colsum, row stride 256 != c")
+
+
+# ------------------------------------------------------------------------------------------------ heads at product shapes
+SGEMM_SHAPES = [(1, 1, 4), (1, 1, 33000), (33, 65, 100), (70, 512, 2048), (64, 512, 1024), (1024, 512, 32)]
+
+
+def _sgemm_plan(m, n, k):
+    """(S, L) of mc_sgemm's launch: S split-K partials (mc_sgemm_ws_floats = S * m * n, 0 when unsplit) and the longest
+    serial accumulation chain L: k, or sgemm_k's k range per split, ceil(k / S) rounded up to the 32-wide k tile"""
+    ws = L.load().mc_sgemm_ws_floats(m, n, k)
+    S = ws // (m * n) if ws else 1
+    kper = -(-(-(-k // S)) // 32) * 32
+    return S, (kper if S > 1 else k)
+
+
+@pytest.mark.parametrize("layout", ["nt", "tn"])
+@pytest.mark.parametrize("m,n,k", SGEMM_SHAPES)
+def test_sgemm_product_shapes(m, n, k, layout):
+    """the layouts loss/_infonce.py, projection.py and evaluator.py call mc_sgemm with: dot product over b * D (32 splits),
+    k = 4, k = batch, m / n across a 32-wide tile, split-K with beta = 1 through the finish kernel, alpha_dev, bias, ldc > n.
+
+    Bound, per element, worst case for fp32 (u = 2^-24), so a correct kernel cannot miss it and a single-element result near
+    zero (m = n = 1) is not divided by itself:
+      * a chain of L fused multiply-adds rounds L times: |acc - sum a b| <= L u sum|a||b|             (first order in u)
+      * the finish kernel adds S partials in order: S - 1 more roundings of partial sums, each <= sum|a||b|
+      * alpha * acc rounds once (alpha itself = fp32(alpha) * alpha_dev is formed here exactly as the kernel forms it)
+      => |alpha| (L + S) u (|A| @ |B|) = g |alpha| (|A| @ |B|),   g = (L + S) 2^-24,  L = k range per split (k when unsplit)
+      * "+ bias" and "+ beta c" round once each, at most u times the magnitude of what they add up:
+        + u (|alpha| |A| @ |B| + |bias| + |c|) per epilogue add."""
+    assert sum(_sgemm_plan(*shp)[0] > 1 for shp in SGEMM_SHAPES) >= 2
+    S, chain = _sgemm_plan(m, n, k)
+    u = 2.0 ** -24
+    g = (chain + S) * u
+    A, B = rnd(m, k, seed=660, dtype=torch.float32), rnd(k, n, seed=661, dtype=torch.float32)
+    if layout == "nt":                                           # a [m, k] and b [n, k] row-major: a @ b.T
+        a_st, ars, acs, b_st, brs, bcs = A, k, 1, B.t().contiguous(), 1, k
+    else:                                                        # a [k, m] and b [k, n] row-major: a.T @ b
+        a_st, ars, acs, b_st, brs, bcs = A.t().contiguous(), 1, m, B, n, 1
+    prod = A.double() @ B.double()
+    mag = A.double().abs() @ B.double().abs()
+
+    def within(got, ref, tol, what):
+        assert torch.isfinite(got).all(), what + ": non-finite"
+        excess = float(((got.double() - ref).abs() - tol).max())
+        print(f"sgemm {layout} {m}x{n}x{k} S={S} L={chain} {what}: max err / bound "
+              f"{float(((got.double() - ref).abs() / tol.clamp_min(1e-300)).max()):.3f}")
+        assert excess <= 0.0, f"{what}: |err| exceeds the bound by {excess:.3e}"
+
+    c = torch.full((m, n), float("nan"), device=DEV)
+    ops.sgemm(a_st, ars, acs, b_st, brs, bcs, c, n, m, n, k)
+    within(c, prod, g * mag, "plain")
+    # device scalar x host alpha, bias; c = columns 2 .. 2 + n of a wider buffer, NaN there (beta = 0 must not read c)
+    ldc = n + 5
+    sd = torch.tensor([14.285], device=DEV)
+    alpha = float((torch.tensor(0.5, device=DEV) * sd).double())
+    bias = rnd(n, seed=662, dtype=torch.float32)
+    wide = torch.full((m, ldc), 123.0, device=DEV)
+    wide[:, 2:2 + n] = float("nan")
+    ops.sgemm(a_st, ars, acs, b_st, brs, bcs, wide[:, 2:], ldc, m, n, k, alpha=0.5, bias=bias, alpha_dev=sd)
+    amag = abs(alpha) * mag
+    within(wide[:, 2:2 + n], alpha * prod + bias.double(), g * amag + u * (amag + bias.double().abs()), "alpha_dev + bias, ldc > n")
+    assert bool((wide[:, :2] == 123.0).all()) and bool((wide[:, 2 + n:] == 123.0).all())
+    # beta = 1 into a non-zero c (split shapes: through the finish kernel), ldc > n
+    wide0 = rnd(m, ldc, seed=663, dtype=torch.float32)
+    wide = wide0.clone()
+    ops.sgemm(a_st, ars, acs, b_st, brs, bcs, wide[:, 2:], ldc, m, n, k, beta=1.0)
+    c0 = wide0[:, 2:2 + n].double()
+    within(wide[:, 2:2 + n], prod + c0, g * mag + u * (mag + c0.abs()), "beta = 1, ldc > n")
+    assert torch.equal(wide[:, :2], wide0[:, :2]) and torch.equal(wide[:, 2 + n:], wide0[:, 2 + n:])
+
+
+CE_CASES = [(r, n) for r in (1, 5, 300) for n in (1, 64, 65, 200, 1000) if r <= n]     # (the arange labels must fit)
+
+
+def _ce_ref64(logits, labels, w, smoothing):
+    lg = logits.double().requires_grad_(True)
+    loss = w * F.cross_entropy(lg, labels, label_smoothing=smoothing)
+    loss.backward()
+    return loss.detach(), lg.grad
+
+
+def _check_dlogits(got, ref, scale, what):
+    """the file's 1e-4 of max|ref|, plus the rounding floor of (p - target - eps / n) * scale: three terms <= 1 held in fp32
+    cancel to +-4 * 2^-24 at best.  That is 0.25 % of the bound wherever max|ref| ~ scale; it matters for n = 1 only, where
+    the exact gradient is 0 and a bound relative to max|ref| = 0 would ask for an exact cancellation."""
+    assert got.shape == ref.shape and torch.isfinite(got).all(), what
+    err, bound = float((got.double() - ref).abs().max()), 1e-4 * float(ref.abs().max()) + 4 * 2.0 ** -24 * scale
+    print(f"{what}: max err {err:.3e} (bound {bound:.3e})")
+    assert err <= bound, f"{what}: max err {err:.3e} > {bound:.3e}"
+
+
+@pytest.mark.parametrize("smoothing", [0.0, 0.1])
+@pytest.mark.parametrize("rows,n", CE_CASES)
+def test_ce_fwd_bwd_shapes(rows, n, smoothing):
+    """one wave per row strides the n columns by 64, one workgroup sums the row losses by 256: n = 1 / 64 / 65 / 200 / 1000,
+    rows = 1 / 5 / 300, logits within +-30 (what logit_scale reaches), against fp64 F.cross_entropy"""
+    w = 0.25
+    logits = 30 * torch.tanh(rnd(rows, n, seed=670, dtype=torch.float32))
+    off = (n - rows) // 2
+    lref, gref = _ce_ref64(logits, torch.arange(rows, device=DEV) + off, w, smoothing)
+    buf, loss = logits.clone(), torch.zeros(1, device=DEV)
+    ops.ce_fwd_bwd(buf, off, w, loss, smoothing=smoothing)
+    check(loss[0], lref, 1e-5, "ce loss, arange labels")
+    _check_dlogits(buf, gref, w / rows, "ce dlogits, arange labels")
+    # explicit labels (a permutation), the loss added into a slot that already holds 3.5
+    labels = torch.randperm(n, generator=torch.Generator().manual_seed(671))[:rows].to(DEV)
+    lref, gref = _ce_ref64(logits, labels, w, smoothing)
+    buf, loss = logits.clone(), torch.full((1,), 3.5, device=DEV)
+    ops.ce_fwd_bwd(buf, 0, w, loss, smoothing=smoothing, labels=labels)
+    check(loss[0], lref + 3.5, 1e-5, "ce loss, explicit labels, non-zero slot")
+    _check_dlogits(buf, gref, w / rows, "ce dlogits, explicit labels")
+
+
+def test_ce_out_of_range_labels():
+    """labels = n and labels = -1 on one row each: the loss is NaN, the other rows' dlogits are what they would be, nothing
+    beside the rows is touched (the logits are the middle rows of a larger buffer: no access can leave the allocation)"""
+    rows, n, guard, w = 5, 65, 2, 0.25
+    logits = 30 * torch.tanh(rnd(rows, n, seed=672, dtype=torch.float32))
+    whole = torch.full((rows + 2 * guard, n), 77.0, device=DEV)
+    whole[guard:guard + rows] = logits
+    labels = torch.tensor([3, n, 10, -1, 64], device=DEV)
+    loss = torch.zeros(1, device=DEV)
+    ops.ce_fwd_bwd(whole[guard:guard + rows], 0, w, loss, labels=labels)
+    assert bool(torch.isnan(loss[0]))
+    good = torch.tensor([0, 2, 4], device=DEV)
+    lg = logits[good].double().requires_grad_(True)
+    (w / rows * F.cross_entropy(lg, labels[good], reduction="sum")).backward()
+    got = whole[guard:guard + rows]
+    assert torch.isfinite(got).all()
+    _check_dlogits(got[good], lg.grad, w / rows, "ce dlogits beside an out-of-range row")
+    assert bool((whole[:guard] == 77.0).all()) and bool((whole[guard + rows:] == 77.0).all())
+
+
+@pytest.mark.parametrize("d", [8, 63, 64, 65, 512, 1000])
+@pytest.mark.parametrize("rows", [1, 5, 130])
+def test_l2norm_shapes(rows, d):
+    """one wave per row strides d by 64, four rows per workgroup: d below / at / above a wave, rows = 130 ends in half a
+    workgroup; against fp64"""
+    a = rnd(rows, d, seed=680, dtype=torch.float32)
+    ar = a.double().requires_grad_(True)
+    yref = ar / ar.norm(dim=1, keepdim=True)
+    y, nrm = ops.l2norm_fwd(a)
+    check(y, yref.detach(), 1e-5, "l2norm")
+    check(nrm, ar.detach().norm(dim=1), 1e-5, "l2norm norm")
+    dy = rnd(rows, d, seed=681, dtype=torch.float32)
+    yref.backward(dy.double())
+    check(ops.l2norm_bwd(dy, y, nrm), ar.grad, 1e-4, "l2norm bwd")
+
+
+def test_eos_all_zero_mask_row():
+    """a row without any real token: sum(mask) - 1 = -1, which the reference uses as a Python index -- the LAST position
+    [ref: model/clip.py:67-68]"""
+    b, t, h = 3, 16, 64
+    lens = torch.tensor([5, 0, 16], device=DEV)
+    mask = (torch.arange(t, device=DEV)[None] < lens[:, None]).long()
+    hid = rnd(b * t, h, seed=690)
+    hv = hid.view(b, t, h)
+    out = ops.eos_gather(hid, mask, b, t, h)
+    assert torch.equal(out[1], hv[:, -1][1].float())
+    assert torch.equal(out, hv[torch.arange(b, device=DEV), lens - 1].float())
+    d = rnd(b, h, seed=691, dtype=torch.float32)
+    want = torch.zeros(b, t, h, device=DEV, dtype=BF)
+    want[torch.arange(b, device=DEV), lens - 1] = d.to(BF)
+    assert torch.equal(ops.eos_scatter(d, mask, b, t, h).view(b, t, h), want)

@@ -169,9 +169,20 @@ def test_varlen_attention_drops_what_the_padded_kernel_drops(lengths, T, nh):
     assert torch.equal(dqkv_p, ops.attn_varlen_bwd(qkv_p, pk, dctx_p, lse_p, nh, 0.125, p, seed, sid))
 
 
-def test_row_mapped_add_ln_and_embedding_are_bit_exact():
+def _lengths_past_the_row_caps():
+    """40 reports at T = 256 with more than 8192 real tokens, lengths 1 and 256 among them: the padded (10240 rows) and the
+    packed layout both leave the first pass of the add+LayerNorm / embedding forward (8192 rows) and run the add+LayerNorm
+    backward (2048 rows per pass) five times; the embedding backward takes 8 sequences per round"""
+    g = torch.Generator().manual_seed(31)
+    lengths = [1, 256] + torch.randint(200, 257, (38,), generator=g).tolist()
+    assert len(lengths) == 40 and sum(lengths) > 8192
+    return lengths
+
+
+@pytest.mark.parametrize("lengths,T", [([12, 1, 40, 7, 33], 40), (_lengths_past_the_row_caps(), 256)], ids=["T40", "T256-past-the-caps"])
+def test_row_mapped_add_ln_and_embedding_are_bit_exact(lengths, T):
     """per-row arithmetic with the padded layout's dropout indices: against the padded kernels, bit-exact on the real rows"""
-    lengths, T, h, p, seed, sid = [12, 1, 40, 7, 33], 40, 768, 0.1, 99, 17
+    h, p, seed, sid = 768, 0.1, 99, 17
     b = len(lengths)
     x, xp, pk, mask, real = _padded_and_packed(lengths, T, h, 1)
     res, resp, *_ = _padded_and_packed(lengths, T, h, 2)
@@ -193,7 +204,7 @@ def test_row_mapped_add_ln_and_embedding_are_bit_exact():
     V = 500
     ids = (torch.randint(1, V, (b, T), generator=g).to(DEV) * mask).contiguous()
     tt = (torch.randint(0, 2, (b, T), generator=g).to(DEV) * mask).contiguous()
-    word, pos, typ = (rnd(n, h, seed=10 + i, dtype=torch.float32) for i, n in enumerate((V, 64, 2)))
+    word, pos, typ = (rnd(n, h, seed=10 + i, dtype=torch.float32) for i, n in enumerate((V, max(64, T), 2)))
     ids_p, tt_p = ids.view(-1)[pk.src.long()].contiguous(), tt.view(-1)[pk.src.long()].contiguous()
     e, em, er = ops.bert_embed_fwd(ids, tt, word, pos, typ, gamma, beta, 1e-12, p, seed, 15)
     ep, epm, epr = ops.bert_embed_fwd(ids_p, tt_p, word, pos, typ, gamma, beta, 1e-12, p, seed, 15, pk=pk)
