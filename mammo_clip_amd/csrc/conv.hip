@@ -6,7 +6,10 @@
 // of the producing expand conv is applied once per element while staging, zero padding is inserted after the
 // activation), partial output rows / tap accumulators held in registers.  Workgroups are persistent over their work
 // items so the per-channel sum / sum-of-squares for the following training-mode BatchNorm leave the forward kernel
-// as a small [workgroups][2][C] partial buffer (deterministic, no atomics).  The stride-2 data gradient is a gather.
+// as a small [workgroups][2][C] partial buffer (deterministic, no atomics).  The stride-2 data gradient is a marching kernel
+// too (a stride-1 stencil over 2x2 "super pixels", with the BatchNorm-backward epilogue and, for the 3x3 blocks, the form that
+// builds e from the block input); the gather kernel below is the independent form the tests compare against and serves
+// stride 1 without flipped taps.
 #include "common_hip.h"
 #include <atomic>
 #include <type_traits>
@@ -93,14 +96,77 @@ template <int K, int S, int CPL, int LP, int NCOL_ = 2> struct MarchCfg {
     static constexpr int NV = (RB * IW_T * VPP + TS - 1) / TS;
     static constexpr int BUF_BYTES = RB * IWP * PSB;
     static constexpr int OCC = (K == 3 && S == 1) ? 3 : 2;           // workgroups per CU the register budget is set for
+    static constexpr int in_rows(int nrows) { return (nrows - 1) * S + K; }      // staged rows behind nrows output rows
 };
 
-#ifdef MARCH_PROF
-__device__ unsigned long long g_march_prof[8];     // developer phase profile (scripts/dwbench.hip)
-#define MPROF(i) do { unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[i] += t_ - tprof; tprof = t_; } while (0)
-#else
-#define MPROF(i)
-#endif
+// ------------------------------------------------------------------------------------------------------------
+// Staging pieces shared by the three marching kernels (C = MarchCfg or MarchBwdCfg).  They take what the kernels' staging
+// lambdas capture BY REFERENCE, and compute exactly what those lambdas spelled out: written that way the compiled kernels are
+// the ones the written-out code gave (by-value parameters, or the same code moved out of a kernel's top level, changed the
+// register allocation of these register-bound kernels; profiles/march_family_ab.md).
+// A staging table entry describes vector tid + i * TS of a tile: row | col << 8 | (LDS byte offset / 16) << 16; row 0xff
+// marks an entry beyond the tile (never valid).
+
+// work item -> (image, first column, first row, rows, staged blocks): items are (image, column strip, row segment), `rows` is
+// what the segments split (output rows, or super-rows of the stride-2 data gradient)
+template <typename C> __device__ __forceinline__ void item_geom(int it, const int& strips, const int& segs, const int& seg_rows, const int& rows,
+                                                                int& img, int& x0, int& y0, int& nrows, int& nblk) {
+    const int strip = it % strips;
+    const int seg = (it / strips) % segs;
+    img = it / (strips * segs);
+    x0 = strip * C::TOW;
+    y0 = seg * seg_rows;
+    nrows = rows - y0 < seg_rows ? rows - y0 : seg_rows;
+    nblk = (C::in_rows(nrows) + C::RB - 1) / C::RB;
+}
+// per item: the table entries whose column x0 + col lies inside a map of the given width
+template <int NV> __device__ __forceinline__ void stage_colmask(unsigned& m, const unsigned (&meta)[NV], const bool& st_ok, int x0, const int& width) {
+    m = 0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int ix = x0 + (int)((meta[i] >> 8) & 0xffu);
+        if (st_ok && ix >= 0 && ix < width) m |= 1u << i;
+    }
+}
+// global -> registers for the tile whose entry (0, 0) is at org = row r0 of a map of `rows` rows.  Unconditional loads
+// (padding / out-of-tile vectors read the harmless valid address `safe` and are zeroed when stored): straight-line code
+// keeps all loads of the block in flight together.  inb: the vectors that hold real pixels.
+template <int NV> __device__ __forceinline__ void tile_load(uint4 (&vals)[NV], const unsigned (&meta)[NV], unsigned& inb, const unsigned& colmask,
+                                                           const bf16_t* const& org, const bf16_t* const& safe, const long long& row_pitch,
+                                                           const int& pix_pitch, const int& vv, const int& r0, const int& rows) {
+    inb = 0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int iy = r0 + (int)(meta[i] & 0xffu);
+        const bool ok = ((colmask >> i) & 1u) && iy >= 0 && iy < rows;
+        const unsigned goff = (meta[i] & 0xffu) * (unsigned)row_pitch + ((meta[i] >> 8) & 0xffu) * (unsigned)pix_pitch + vv * 8;
+        const bf16_t* a = ok ? org + goff : safe;
+        vals[i] = *reinterpret_cast<const uint4*>(a);
+        inb |= (ok ? 1u : 0u) << i;
+    }
+}
+// registers -> LDS; has_pro: with the fused BN+SiLU prologue (pro_s / pro_t: the thread's 8 scale / shift values) on real
+// pixels (zero padding stays zero).  The caller waits for the loads first (explicit vmcnt(0), see the forward kernel).
+template <int NV> __device__ __forceinline__ void tile_store(unsigned char* lds, const uint4 (&vals)[NV], const unsigned (&meta)[NV],
+                                                             unsigned inb, bool ts_ok, bool has_pro = false,
+                                                             const float* pro_s = nullptr, const float* pro_t = nullptr) {
+    float ps[8], pt[8];
+    if (has_pro) { load8f(pro_s, ps); load8f(pro_t, pt); }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (ts_ok && (meta[i] & 0xffu) != 0xffu) {
+            const bool real = (inb >> i) & 1u;
+            uint4 val = real ? vals[i] : make_uint4(0u, 0u, 0u, 0u);
+            if (has_pro && real) {
+                float f[8];
+                unpack8(val, f);
+                bn_silu8(f, ps, pt);
+                val = pack8(f);
+            }
+            *reinterpret_cast<uint4*>(lds + ((meta[i] >> 16) << 4)) = val;
+        }
+    }
+}
 
 // EPI (stride 1 only): the launch is the DATA GRADIENT of a depthwise conv whose input was silu(bn0(e)) -- the output of
 // this "forward on flipped taps" is dA0, and the kernel finishes the step that follows it in the MBConv backward
@@ -210,14 +276,8 @@ __global__ __launch_bounds__(256, (K == 3 && S == 1 && !EPI ? 3 : 2)) void dwcon
     const int pix_pitch = p.c;
 
     const int nitems = p.n * strips * segs;
-    auto item_geom = [&](int it, int& img, int& ox0, int& oy0, int& nrows, int& nblk) {
-        const int strip = it % strips;
-        const int seg = (it / strips) % segs;
-        img = it / (strips * segs);
-        ox0 = strip * C::TOW;
-        oy0 = seg * seg_rows;
-        nrows = p.oh - oy0 < seg_rows ? p.oh - oy0 : seg_rows;
-        nblk = ((nrows - 1) * S + K + C::RB - 1) / C::RB;
+    auto geom = [&](int it, int& img, int& ox0, int& oy0, int& nrows, int& nblk) {
+        item_geom<C>(it, strips, segs, seg_rows, p.oh, img, ox0, oy0, nrows, nblk);
     };
 
     uint4 vals[C::NV];
@@ -229,27 +289,9 @@ __global__ __launch_bounds__(256, (K == 3 && S == 1 && !EPI ? 3 : 2)) void dwcon
     // global -> registers for block b of item (img, ox0, oy0)
     auto stage_load = [&](int img, int ox0, int oy0, int b, bool new_item) {
         const int iy0 = oy0 * S - p.pad_t + b * C::RB, ix0 = ox0 * S - p.pad_l;
-        if (new_item) {
-            colmask = 0;
-#pragma unroll
-            for (int i = 0; i < C::NV; ++i) {
-                const int ix = ix0 + (int)((meta[i] >> 8) & 0xffu);
-                if (st_ok && ix >= 0 && ix < p.w) colmask |= 1u << i;
-            }
-        }
+        if (new_item) stage_colmask(colmask, meta, st_ok, ix0, p.w);
         const bf16_t* org = p.x + ((long long)img * p.h + iy0) * in_row_pitch + (long long)ix0 * p.c + c0;
-        inb = 0;
-#pragma unroll
-        for (int i = 0; i < C::NV; ++i) {
-            // unconditional load (padding / out-of-tile vectors read a harmless valid address and are zeroed when
-            // stored): straight-line code keeps all loads of the block in flight together
-            const int iy = iy0 + (int)(meta[i] & 0xffu);
-            const bool ok = ((colmask >> i) & 1u) && iy >= 0 && iy < p.h;
-            const unsigned goff = (meta[i] & 0xffu) * (unsigned)in_row_pitch + ((meta[i] >> 8) & 0xffu) * (unsigned)p.c + vv * 8;
-            const bf16_t* a = ok ? org + goff : p.x;
-            vals[i] = *reinterpret_cast<const uint4*>(a);
-            inb |= (ok ? 1u : 0u) << i;
-        }
+        tile_load(vals, meta, inb, colmask, org, p.x, in_row_pitch, p.c, vv, iy0, p.h);
         if constexpr (EPI) {
             // e rows of the output rows block b completes: o = b*RB - (K-1) + row  (only rows / columns that exist)
             const int o0 = b * C::RB - (K - 1);
@@ -271,22 +313,7 @@ __global__ __launch_bounds__(256, (K == 3 && S == 1 && !EPI ? 3 : 2)) void dwcon
         // bookkeeping treats the prefetched registers as possibly-pending on later paths and drains the NEXT block's
         // loads (vmcnt(0)) right before the compute loop, which serialises load latency with compute
         __builtin_amdgcn_s_waitcnt(0x0F70);
-        float ps[8], pt[8];
-        if (has_pro) { load8f(&pro_lds[0][vv * 8], ps); load8f(&pro_lds[1][vv * 8], pt); }
-#pragma unroll
-        for (int i = 0; i < C::NV; ++i) {
-            if (tid < C::TS && (meta[i] & 0xffu) != 0xffu) {
-                const bool real = (inb >> i) & 1u;
-                uint4 val = real ? vals[i] : make_uint4(0u, 0u, 0u, 0u);
-                if (has_pro && real) {
-                    float f[8];
-                    unpack8(val, f);
-                    bn_silu8(f, ps, pt);
-                    val = pack8(f);
-                }
-                *reinterpret_cast<uint4*>(smem + ((meta[i] >> 16) << 4)) = val;
-            }
-        }
+        tile_store(smem, vals, meta, inb, tid < C::TS, has_pro, &pro_lds[0][vv * 8], &pro_lds[1][vv * 8]);
         if constexpr (EPI) {
 #pragma unroll
             for (int i = 0; i < NVE; ++i)
@@ -298,31 +325,23 @@ __global__ __launch_bounds__(256, (K == 3 && S == 1 && !EPI ? 3 : 2)) void dwcon
     int it = y, img = 0;
     int ox0 = 0, oy0 = 0, nrows = 0, nblk = 0, b = 0;
     if (it >= nitems) return;                 // (never: gy <= nitems)
-    item_geom(it, img, ox0, oy0, nrows, nblk);
+    geom(it, img, ox0, oy0, nrows, nblk);
     nrows_l = nrows;
     stage_load(img, ox0, oy0, 0, true);
-#ifdef MARCH_PROF
-    unsigned long long pacc[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long tprof = __builtin_amdgcn_s_memtime();
-#endif
     while (true) {
         __syncthreads();                       // previous block fully consumed
-        MPROF(0);
         stage_store();
-        MPROF(1);
         __syncthreads();
-        MPROF(2);
         // prefetch the block after (it, b) while this one computes
         int it2 = it, img2 = img;
         int ox2 = ox0, oy2 = oy0, nrows2 = nrows, nblk2 = nblk, b2 = b + 1;
         if (b2 >= nblk) {
             it2 = it + gy; b2 = 0;
-            if (it2 < nitems) item_geom(it2, img2, ox2, oy2, nrows2, nblk2);
+            if (it2 < nitems) geom(it2, img2, ox2, oy2, nrows2, nblk2);
         }
         const bool more = it2 < nitems;
         nrows_l = nrows2;
         if (more) stage_load(img2, ox2, oy2, b2, b2 == 0);
-        MPROF(3);
 
         if (b == 0) {                          // new item: clear the accumulators, aim the running output row pointer
 #pragma unroll
@@ -416,18 +435,10 @@ __global__ __launch_bounds__(256, (K == 3 && S == 1 && !EPI ? 3 : 2)) void dwcon
                 }
             }
         }
-        MPROF(4);
-#ifdef MARCH_PROF
-        pacc[5] += 1;
-#endif
         if (!more) break;
         it = it2; img = img2; ox0 = ox2; oy0 = oy2; nrows = nrows2; nblk = nblk2; b = b2;
     }
 
-#ifdef MARCH_PROF
-    if (tid == 0)
-        for (int i = 0; i < 6; ++i) atomicAdd(&g_march_prof[i], pacc[i]);
-#endif
     if (p.stat_partials) {
         __syncthreads();
         float* red = reinterpret_cast<float*>(smem);          // [256 threads][2][CPL]
@@ -525,14 +536,8 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bww_kernel(const mc_dwcon
     f32x2_t g[C::A][NCOL][C::H2];
 
     const int nitems = p.n * strips * segs;
-    auto item_geom = [&](int it, int& img, int& ox0, int& oy0, int& nrows, int& nblk) {
-        const int strip = it % strips;
-        const int seg = (it / strips) % segs;
-        img = it / (strips * segs);
-        ox0 = strip * C::TOW;
-        oy0 = seg * seg_rows;
-        nrows = p.oh - oy0 < seg_rows ? p.oh - oy0 : seg_rows;
-        nblk = ((nrows - 1) * S + K + C::RB - 1) / C::RB;
+    auto geom = [&](int it, int& img, int& ox0, int& oy0, int& nrows, int& nblk) {
+        item_geom<C>(it, strips, segs, seg_rows, p.oh, img, ox0, oy0, nrows, nblk);
     };
 
     uint4 vals[C::NV], gvals[NVG];
@@ -540,32 +545,18 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bww_kernel(const mc_dwcon
     auto stage_load = [&](int img, int ox0, int oy0, int nrows, int b, bool new_item) {
         const int iy0 = oy0 * S - p.pad_t + b * C::RB, ix0 = ox0 * S - p.pad_l;
         if (new_item) {
-            colmask = 0; gcolmask = 0;
-#pragma unroll
-            for (int i = 0; i < C::NV; ++i) {
-                const int ix = ix0 + (int)((meta[i] >> 8) & 0xffu);
-                if (st_ok && ix >= 0 && ix < p.w) colmask |= 1u << i;
-            }
+            stage_colmask(colmask, meta, st_ok, ix0, p.w); gcolmask = 0;
 #pragma unroll
             for (int i = 0; i < NVG; ++i)
                 if (st_ok && ox0 + (int)((metag[i] >> 8) & 0xffu) < p.ow) gcolmask |= 1u << i;
         }
         const bf16_t* org = p.x + ((long long)img * p.h + iy0) * in_row_pitch + (long long)ix0 * p.c + c0;
-        inb = 0;
-#pragma unroll
-        for (int i = 0; i < C::NV; ++i) {
-            const int iy = iy0 + (int)(meta[i] & 0xffu);
-            const bool ok = ((colmask >> i) & 1u) && iy >= 0 && iy < p.h;
-            const unsigned goff = (meta[i] & 0xffu) * (unsigned)in_row_pitch + ((meta[i] >> 8) & 0xffu) * (unsigned)p.c + vv * 8;
-            const bf16_t* a = ok ? org + goff : p.x;
-            vals[i] = *reinterpret_cast<const uint4*>(a);
-            inb |= (ok ? 1u : 0u) << i;
-        }
+        tile_load(vals, meta, inb, colmask, org, p.x, in_row_pitch, p.c, vv, iy0, p.h);
         const int o0 = b * ORB;
         const bf16_t* gorg = p.dy + ((long long)img * p.oh + oy0 + o0) * g_row_pitch + (long long)ox0 * p.c + c0;
         ginb = 0;
 #pragma unroll
-        for (int i = 0; i < NVG; ++i) {
+        for (int i = 0; i < NVG; ++i) {                    // (as tile_load, without a lower row bound: o0 >= 0)
             const int o = o0 + (int)(metag[i] & 0xffu);
             const bool ok = ((gcolmask >> i) & 1u) && o < nrows;
             const unsigned goff = (metag[i] & 0xffu) * (unsigned)g_row_pitch + ((metag[i] >> 8) & 0xffu) * (unsigned)p.c + vv * 8;
@@ -592,19 +583,13 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bww_kernel(const mc_dwcon
                 *reinterpret_cast<uint4*>(smem + ((meta[i] >> 16) << 4)) = val;
             }
         }
-#pragma unroll
-        for (int i = 0; i < NVG; ++i) {
-            if (tid < C::TS && (metag[i] & 0xffu) != 0xffu) {
-                const uint4 val = ((ginb >> i) & 1u) ? gvals[i] : make_uint4(0u, 0u, 0u, 0u);
-                *reinterpret_cast<uint4*>(gsm + ((metag[i] >> 16) << 4)) = val;
-            }
-        }
+        tile_store(gsm, gvals, metag, ginb, tid < C::TS);
     };
 
     int it = y, img = 0;
     int ox0 = 0, oy0 = 0, nrows = 0, nblk = 0, b = 0;
     if (it >= nitems) return;
-    item_geom(it, img, ox0, oy0, nrows, nblk);
+    geom(it, img, ox0, oy0, nrows, nblk);
     stage_load(img, ox0, oy0, nrows, 0, true);
     while (true) {
         __syncthreads();
@@ -614,7 +599,7 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bww_kernel(const mc_dwcon
         int ox2 = ox0, oy2 = oy0, nrows2 = nrows, nblk2 = nblk, b2 = b + 1;
         if (b2 >= nblk) {
             it2 = it + gy; b2 = 0;
-            if (it2 < nitems) item_geom(it2, img2, ox2, oy2, nrows2, nblk2);
+            if (it2 < nitems) geom(it2, img2, ox2, oy2, nrows2, nblk2);
         }
         const bool more = it2 < nitems;
         if (more) stage_load(img2, ox2, oy2, nrows2, b2, b2 == 0);
@@ -710,12 +695,16 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bww_kernel(const mc_dwcon
 // touches (all K*K taps of the lane's channels, held in registers, are used once per dy row), and super-row o' is
 // complete - four output pixels per super-column - as soon as dy row o' has been processed.  The kernel is bound by
 // the 4x larger dx write stream.
-template <int K, int CPL, int LP, int NJ, bool EPI = false> struct MarchBwdCfg {
+template <int K_, int CPL_, int LP_, int NJ_, bool EPI_ = false> struct MarchBwdCfg {
+    static constexpr int K = K_, CPL = CPL_, LP = LP_, NJ = NJ_;
+    static constexpr bool EPI = EPI_;
     static constexpr int H2 = CPL / 2;
     static constexpr int PXW = 64 / LP;
     static constexpr int D = (K + 1) / 2;                  // super-taps per dimension = live super-rows
-    static constexpr int TOWJ = 4 * PXW * NJ;              // super-columns per strip
-    static constexpr int IW_T = TOWJ + D - 1;              // staged dy columns
+    static constexpr int TOWJ = 4 * PXW * NJ, TOW = TOWJ;  // super-columns per strip
+    static constexpr int IW_T = TOWJ + D - 1, IWP = IW_T;  // staged dy columns (dense, no swizzle)
+    static constexpr bool SWZ = false;
+    static constexpr int SWZ_BIT = 0;
     static constexpr int NIN = NJ + D - 1;
     static constexpr int TCH = LP * CPL;
     static constexpr int PXB = TCH * 2;
@@ -730,6 +719,7 @@ template <int K, int CPL, int LP, int NJ, bool EPI = false> struct MarchBwdCfg {
     static constexpr int TS = 256 - 256 % VPP;
     static constexpr int NV = (RB * IW_T * VPP + TS - 1) / TS;
     static constexpr int BUF_BYTES = RB * IW_T * PSB;
+    static constexpr int in_rows(int nrows) { return nrows + D - 1; }      // dy rows s0-(D-1) .. s0+nrows-1 behind nrows super-rows
 };
 
 // EPI: the launch also finishes the BatchNorm0 + SiLU backward of the expand conv output e = p.epi_x [n,h,w,c] (see the
@@ -774,7 +764,6 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
     const int jl0 = (wave * C::PXW + (lane_ok ? px : 0)) * NJ;       // strip-local first super-column
     const int lbase = jl0 * C::PSB + lq * (CPL * 2);
     const int ohv = (p.h + p.pad_t + 1) >> 1;              // super-rows / super-columns that cover the image
-    const int owv = (p.w + p.pad_l + 1) >> 1;
 
     f32x2_t w[K * K][C::H2];
 #pragma unroll
@@ -837,14 +826,8 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
     }
 
     const int nitems = p.n * strips * segs;
-    auto item_geom = [&](int it, int& img, int& j0, int& s0, int& nrows, int& nblk) {
-        const int strip = it % strips;
-        const int seg = (it / strips) % segs;
-        img = it / (strips * segs);
-        j0 = strip * C::TOWJ;
-        s0 = seg * seg_rows;
-        nrows = ohv - s0 < seg_rows ? ohv - s0 : seg_rows;             // super-rows owned by the item
-        nblk = (nrows + C::D - 1 + C::RB - 1) / C::RB;                 // dy rows s0-(D-1) .. s0+nrows-1
+    auto geom = [&](int it, int& img, int& j0, int& s0, int& nrows, int& nblk) {
+        item_geom<C>(it, strips, segs, seg_rows, ohv, img, j0, s0, nrows, nblk);
     };
     uint4 vals[C::NV];
     unsigned inb = 0, colmask = 0;
@@ -891,36 +874,13 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
     };
     auto stage_load = [&](int img, int j0, int s0, int b, bool new_item) {
         const int oy0 = s0 - (C::D - 1) + b * C::RB, ox0 = j0 - (C::D - 1);
-        if (new_item) {
-            colmask = 0;
-#pragma unroll
-            for (int i = 0; i < C::NV; ++i) {
-                const int ox = ox0 + (int)((meta[i] >> 8) & 0xffu);
-                if (st_ok && ox >= 0 && ox < p.ow) colmask |= 1u << i;
-            }
-        }
+        if (new_item) stage_colmask(colmask, meta, st_ok, ox0, p.ow);
         const bf16_t* org = p.dy + ((long long)img * p.oh + oy0) * g_row_pitch + (long long)ox0 * p.c + c0;
-        inb = 0;
-#pragma unroll
-        for (int i = 0; i < C::NV; ++i) {
-            const int oy = oy0 + (int)(meta[i] & 0xffu);
-            const bool ok = ((colmask >> i) & 1u) && oy >= 0 && oy < p.oh;
-            const unsigned goff = (meta[i] & 0xffu) * (unsigned)g_row_pitch + ((meta[i] >> 8) & 0xffu) * (unsigned)p.c + vv * 8;
-            const bf16_t* a = ok ? org + goff : p.dy;
-            vals[i] = *reinterpret_cast<const uint4*>(a);
-            inb |= (ok ? 1u : 0u) << i;
-        }
+        tile_load(vals, meta, inb, colmask, org, p.dy, g_row_pitch, p.c, vv, oy0, p.oh);
     };
     auto stage_store = [&]() {
         __builtin_amdgcn_s_waitcnt(0x0F70);
-#pragma unroll
-        for (int i = 0; i < C::NV; ++i) {
-            if (tid < C::TS && (meta[i] & 0xffu) != 0xffu) {
-                const bool real = (inb >> i) & 1u;
-                const uint4 val = make_uint4(real ? vals[i].x : 0u, real ? vals[i].y : 0u, real ? vals[i].z : 0u, real ? vals[i].w : 0u);
-                *reinterpret_cast<uint4*>(smem + ((meta[i] >> 16) << 4)) = val;
-            }
-        }
+        tile_store(smem, vals, meta, inb, tid < C::TS);
         if constexpr (XW) {
             const uint4* s_w = reinterpret_cast<const uint4*>(smem + AW_OFF);
             unsigned char* et = smem + ET_OFF + wave * ET_WAVE + (lane & 15) * C::PXB + xkg * 8;
@@ -951,7 +911,7 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
 
     int it = y, img = 0, j0 = 0, s0 = 0, nrows = 0, nblk = 0, b = 0;
     if (it >= nitems) return;
-    item_geom(it, img, j0, s0, nrows, nblk);
+    geom(it, img, j0, s0, nrows, nblk);
     stage_load(img, j0, s0, 0, true);
     epi_load(img, j0, s0, nrows, 0);
     int sr_next = 0;                                       // super-row (item-relative) completed by the next dy row
@@ -965,7 +925,7 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
         int it2 = it, img2 = img, j2 = j0, s2 = s0, nrows2 = nrows, nblk2 = nblk, b2 = b + 1;
         if (b2 >= nblk) {
             it2 = it + gy; b2 = 0;
-            if (it2 < nitems) item_geom(it2, img2, j2, s2, nrows2, nblk2);
+            if (it2 < nitems) geom(it2, img2, j2, s2, nrows2, nblk2);
         }
         const bool more = it2 < nitems;
         if (more) { stage_load(img2, j2, s2, b2, b2 == 0); epi_load(img2, j2, s2, nrows2, b2); }
@@ -1172,83 +1132,50 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
     }
 }
 
-template <int K, int CPL, int LP, int NJ, bool EPI = false> int march_bwd_s2_plan(const mc_dwconv_args& p, int* strips_, int* segs_, int* seg_rows_, int* ctiles_) {
-    using C = MarchBwdCfg<K, CPL, LP, NJ, EPI>;
-    const int ohv = (p.h + p.pad_t + 1) >> 1, owv = (p.w + p.pad_l + 1) >> 1;
-    const int strips = mc_div_up(owv, C::TOWJ), ctiles = mc_div_up(p.c, C::TCH);
-    long long base = (long long)p.n * strips * ctiles;
-    int segs = (int)((2048 + base - 1) / base);
-    int max_segs = ohv / 16 > 0 ? ohv / 16 : 1;
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    const int seg_rows = mc_div_up(mc_div_up(ohv, segs), C::RB) * C::RB;
-    segs = mc_div_up(ohv, seg_rows);
-    long long nitems = (long long)p.n * strips * segs;
-    long long per_xcd = 64 / ctiles;                            // 2 workgroups per CU, capped per XCD (see march_plan)
+// ------------------------------------------------------------------------------------------------------------
+// Host side: the work split and the tile choice.
+struct MarchPlan { int strips, segs, seg_rows, ctiles, gy; };
+
+// Persistent workgroups per channel tile: as many as are resident at once, every one with the same item count.
+// Block b runs on XCD b % 8 and the kernels map (b >> 3) -> (channel tile, y / 8): an XCD receives ceil(gy / 8) * ctiles
+// workgroups and holds 32 CUs x wg_per_cu of them.  The y count is capped PER XCD (round 3): the chip-wide cap 256 * OCC /
+// ctiles put 68 workgroups on the 64 slots of XCDs 0-3 at c = 1056 (17 channel tiles, gy = 28): four stragglers ran a
+// second round and the launch took 1.9x the time of the c = 768 launch for 1.4x the work.
+int march_gy(long long nitems, int ctiles, int wg_per_cu) {
+    long long per_xcd = 32 * wg_per_cu / ctiles;
     if (per_xcd < 1) per_xcd = 1;
     long long cap = 8 * per_xcd;
     long long per = (nitems + cap - 1) / cap;
-    *strips_ = strips; *segs_ = segs; *seg_rows_ = seg_rows; *ctiles_ = ctiles;
     return (int)((nitems + per - 1) / per);
 }
-template <int K, int CPL, int LP, int NJ, int KS = 0> int launch_march_bwd_s2_epi(const mc_dwconv_args& p, hipStream_t st) {
-    int strips, segs, seg_rows, ctiles;
-    const int gy = march_bwd_s2_plan<K, CPL, LP, NJ, true>(p, &strips, &segs, &seg_rows, &ctiles);
-    const int gy8 = (gy + 7) / 8 * 8;
-    hipLaunchKernelGGL((dwconv_march_bwd_s2_kernel<K, CPL, LP, NJ, true, KS>), dim3(gy8 * ctiles), dim3(256), 0, st, p, strips, segs,
-                       seg_rows, ctiles, gy);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-template <int K, int CPL, int LP, int NJ> int launch_march_bwd_s2(const mc_dwconv_args& p, hipStream_t st) {
-    using C = MarchBwdCfg<K, CPL, LP, NJ>;
-    const int ohv = (p.h + p.pad_t + 1) >> 1, owv = (p.w + p.pad_l + 1) >> 1;
-    const int strips = mc_div_up(owv, C::TOWJ), ctiles = mc_div_up(p.c, C::TCH);
-    long long base = (long long)p.n * strips * ctiles;
-    int segs = (int)((2048 + base - 1) / base);
-    int max_segs = ohv / 16 > 0 ? ohv / 16 : 1;
+// rows (output rows, or super-rows of the stride-2 data gradient) in segments of whole `unit`s: enough of them for
+// `target` work items, none shorter than min_rows
+void march_segments(MarchPlan& m, const mc_dwconv_args& p, int rows, int unit, int target, int min_rows) {
+    long long base = (long long)p.n * m.strips * m.ctiles;
+    int segs = (int)((target + base - 1) / base);
+    int max_segs = rows / min_rows > 0 ? rows / min_rows : 1;
     if (segs > max_segs) segs = max_segs;
     if (segs < 1) segs = 1;
-    const int seg_rows = mc_div_up(mc_div_up(ohv, segs), C::RB) * C::RB;
-    segs = mc_div_up(ohv, seg_rows);
-    long long nitems = (long long)p.n * strips * segs;
-    long long per_xcd = 64 / ctiles;                            // 2 workgroups per CU, capped per XCD (see march_plan)
-    if (per_xcd < 1) per_xcd = 1;
-    long long cap = 8 * per_xcd;
-    long long per = (nitems + cap - 1) / cap;
-    const int gy = (int)((nitems + per - 1) / per);
-    const int gy8 = (gy + 7) / 8 * 8;
-    hipLaunchKernelGGL((dwconv_march_bwd_s2_kernel<K, CPL, LP, NJ>), dim3(gy8 * ctiles), dim3(256), 0, st, p, strips, segs, seg_rows,
-                       ctiles, gy);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    m.seg_rows = mc_div_up(mc_div_up(rows, segs), unit) * unit;
+    m.segs = mc_div_up(rows, m.seg_rows);
 }
-
-struct MarchPlan { int strips, segs, seg_rows, ctiles, gy; };
 template <typename C> MarchPlan march_plan(const mc_dwconv_args& p) {
     MarchPlan m;
     m.strips = mc_div_up(p.ow, C::TOW);
     m.ctiles = mc_div_up(p.c, C::TCH);
-    long long base = (long long)p.n * m.strips * m.ctiles;
-    int segs = (int)((3072 + base - 1) / base);
-    int max_segs = p.oh / 24 > 0 ? p.oh / 24 : 1;
-    if (segs > max_segs) segs = max_segs;
-    if (segs < 1) segs = 1;
-    m.seg_rows = mc_div_up(mc_div_up(p.oh, segs), C::A * C::NR) * (C::A * C::NR);
-    m.segs = mc_div_up(p.oh, m.seg_rows);
-    // persistent workgroups: as many as are resident at once, every one with the same item count
-    long long nitems = (long long)p.n * m.strips * m.segs;
-    // Block b runs on XCD b % 8 and the kernel maps (b >> 3) -> (channel tile, y / 8): an XCD receives ceil(gy / 8) * ctiles
-    // workgroups and holds 32 CUs x OCC of them.  The y count is capped PER XCD (round 3): the chip-wide cap 256 * OCC /
-    // ctiles put 68 workgroups on the 64 slots of XCDs 0-3 at c = 1056 (17 channel tiles, gy = 28): four stragglers ran a
-    // second round and the launch took 1.9x the time of the c = 768 launch for 1.4x the work.
-    const long long occ = p.epi_x ? 2 : C::OCC;                   // (the epilogue variant is built for 2 workgroups per CU)
-    long long per_xcd = 32 * occ / m.ctiles;
-    if (per_xcd < 1) per_xcd = 1;
-    long long cap = 8 * per_xcd;
-    long long per = (nitems + cap - 1) / cap;
-    m.gy = (int)((nitems + per - 1) / per);
+    march_segments(m, p, p.oh, C::A * C::NR, 3072, 24);
+    // (the epilogue variant is built for 2 workgroups per CU)
+    m.gy = march_gy((long long)p.n * m.strips * m.segs, m.ctiles, p.epi_x ? 2 : C::OCC);
+    return m;
+}
+// the stride-2 data gradient (C = MarchBwdCfg): super-rows and super-columns that cover the image; 2 workgroups per CU
+template <typename C> MarchPlan march_bwd_s2_plan(const mc_dwconv_args& p) {
+    const int ohv = (p.h + p.pad_t + 1) >> 1, owv = (p.w + p.pad_l + 1) >> 1;
+    MarchPlan m;
+    m.strips = mc_div_up(owv, C::TOWJ);
+    m.ctiles = mc_div_up(p.c, C::TCH);
+    march_segments(m, p, ohv, C::RB, 2048, 16);
+    m.gy = march_gy((long long)p.n * m.strips * m.segs, m.ctiles, 2);
     return m;
 }
 
@@ -1261,7 +1188,9 @@ template <int K, int S, typename F> auto march_dispatch(const mc_dwconv_args& p,
         // 480-byte pixels, misaligned with the 128-byte lines on 3 pixels of 4 -- whole pixels (60 lanes x 4 channels, one
         // pixel per wave, 8-column strips whose rows are contiguous 3.8 KB runs) run the forward 1.2-1.35x faster in spite
         // of the 2-in-10 column halo; the weight gradient gains 1.2x once it runs three workgroups per CU (0.725 -> 0.597 ms)
-        if (p.c == 240 && S == 1 && whole_pixels) return f(MarchCfg<K, S, 4, 60>{});
+        if constexpr (S == 1) {
+            if (p.c == 240 && whole_pixels) return f(MarchCfg<K, S, 4, 60>{});
+        }
         // (c = 144, 288-byte pixels: whole-pixel tiles of 36 lanes leave 28 lanes of a wave idle -- 0.85 vs 0.96 ms without the
         // prologue, 1.18 vs 1.07 ms with it; 72-channel tiles of 18 lanes: 0.90 / 1.13 ms: not used)
         if (p.c % 48 == 0 && p.c < 192) return f(MarchCfg<K, S, 4, 12>{});      // 48, 144: exact 48-channel tiles
@@ -1271,36 +1200,37 @@ template <int K, int S, typename F> auto march_dispatch(const mc_dwconv_args& p,
         return f(MarchCfg<K, S, 2, 32, (S == 1 ? 4 : 2)>{});
     }
 }
-template <int K, int S, typename C> int launch_march(const mc_dwconv_args& p, hipStream_t st) {
-    MarchPlan m = march_plan<C>(p);
-    int gy8 = (m.gy + 7) / 8 * 8;
-    if constexpr (S == 1) {
-        if (p.epi_x) {
-            hipLaunchKernelGGL((dwconv_march_fwd_kernel<K, S, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL, true>), dim3(gy8 * m.ctiles), dim3(256),
-                               0, st, p, m.strips, m.segs, m.seg_rows, m.ctiles, m.gy);
-            MC_LAUNCH_CHECK();
-            return MC_OK;
-        }
+// ... and of the stride-2 data gradient: one super-column per lane for k = 3 (48- or 64-channel tiles), two for k = 5
+template <bool EPI, typename F> auto march_bwd_s2_dispatch(const mc_dwconv_args& p, F&& f) {
+    if (p.k == 3) {
+        if (p.c % 48 == 0 && p.c < 192) return f(MarchBwdCfg<3, 4, 12, 1, EPI>{});
+        return f(MarchBwdCfg<3, 4, 16, 1, EPI>{});
     }
-    hipLaunchKernelGGL((dwconv_march_fwd_kernel<K, S, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL>), dim3(gy8 * m.ctiles), dim3(256), 0, st, p,
-                       m.strips, m.segs, m.seg_rows, m.ctiles, m.gy);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
+    return f(MarchBwdCfg<5, 2, 32, 2, EPI>{});
+}
+
+template <int K, int S, typename C> int launch_march(const mc_dwconv_args& p, hipStream_t st) {
+    const MarchPlan m = march_plan<C>(p);
+    auto launch = [&](auto epi) {
+        hipLaunchKernelGGL((dwconv_march_fwd_kernel<K, S, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL, decltype(epi)::value>),
+                           dim3((m.gy + 7) / 8 * 8 * m.ctiles), dim3(256), 0, st, p, m.strips, m.segs, m.seg_rows, m.ctiles, m.gy);
+        MC_LAUNCH_CHECK();
+        return MC_OK;
+    };
+    if constexpr (S == 1) {
+        if (p.epi_x) return launch(std::true_type{});
+    }
+    return launch(std::false_type{});
 }
 template <int K, int S> int launch_march_cp(const mc_dwconv_args& p, hipStream_t st) {
     return march_dispatch<K, S>(p, [&](auto cfg) { return launch_march<K, S, decltype(cfg)>(p, st); }, true);
 }
 template <int K, int S, typename C> int launch_march_bww(const mc_dwconv_args& p, hipStream_t st) {
     MarchPlan m = march_plan<C>(p);
-    long long nitems = (long long)p.n * m.strips * m.segs;      // 2 workgroups per CU here; capped per XCD (see march_plan)
-    long long per_xcd = (C::TCH == 240 ? 96 : 64) / m.ctiles;    // (the whole-pixel form fits three workgroups per CU: 156 VGPRs)
-    if (per_xcd < 1) per_xcd = 1;
-    long long cap = 8 * per_xcd;
-    long long per = (nitems + cap - 1) / cap;
-    m.gy = (int)((nitems + per - 1) / per);
-    int gy8 = (m.gy + 7) / 8 * 8;
-    hipLaunchKernelGGL((dwconv_march_bww_kernel<K, S, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL>), dim3(gy8 * m.ctiles), dim3(256), 0, st,
-                       p, m.strips, m.segs, m.seg_rows, m.ctiles, m.gy);
+    // 2 workgroups per CU here (the whole-pixel form fits three: 156 VGPRs)
+    m.gy = march_gy((long long)p.n * m.strips * m.segs, m.ctiles, C::TCH == 240 ? 3 : 2);
+    hipLaunchKernelGGL((dwconv_march_bww_kernel<K, S, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL>), dim3((m.gy + 7) / 8 * 8 * m.ctiles),
+                       dim3(256), 0, st, p, m.strips, m.segs, m.seg_rows, m.ctiles, m.gy);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
@@ -1309,6 +1239,14 @@ template <int K, int S> int launch_march_bww_cp(const mc_dwconv_args& p, hipStre
 }
 template <int K, int S> int march_rows(const mc_dwconv_args& p) {
     return march_dispatch<K, S>(p, [&](auto cfg) { return march_plan<decltype(cfg)>(p).gy; }, true);
+}
+// KS > 0: the E-free form (3x3 tiles only), KS = 32-channel groups of the block input
+template <typename C, int KS = 0> int launch_march_bwd_s2(const mc_dwconv_args& p, hipStream_t st) {
+    const MarchPlan m = march_bwd_s2_plan<C>(p);
+    hipLaunchKernelGGL((dwconv_march_bwd_s2_kernel<C::K, C::CPL, C::LP, C::NJ, C::EPI, KS>), dim3((m.gy + 7) / 8 * 8 * m.ctiles), dim3(256),
+                       0, st, p, m.strips, m.segs, m.seg_rows, m.ctiles, m.gy);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
 }
 
 int check_common(const mc_dwconv_args& p) {
@@ -1386,11 +1324,9 @@ extern "C" int mc_dwconv_stat_rows(const mc_dwconv_args* a) {
 extern "C" int mc_dwconv_bwd_data_plan(const mc_dwconv_args* a, int* plan) {
     const mc_dwconv_args& p = *a;
     if (p.stride != 2) return 0;
-    if (p.k == 3) {
-        if (p.c % 48 == 0 && p.c < 192) return march_bwd_s2_plan<3, 4, 12, 1, true>(p, plan, plan + 1, plan + 2, plan + 3);
-        return march_bwd_s2_plan<3, 4, 16, 1, true>(p, plan, plan + 1, plan + 2, plan + 3);
-    }
-    return march_bwd_s2_plan<5, 2, 32, 2, true>(p, plan, plan + 1, plan + 2, plan + 3);
+    const MarchPlan m = march_bwd_s2_dispatch<true>(p, [&](auto cfg) { return march_bwd_s2_plan<decltype(cfg)>(p); });
+    plan[0] = m.strips; plan[1] = m.segs; plan[2] = m.seg_rows; plan[3] = m.ctiles;
+    return m.gy;
 }
 // rows of stat_partials written by mc_dwconv_bwd_data with the stride-2 BatchNorm-backward epilogue (epi_x set)
 extern "C" int mc_dwconv_bwd_data_stat_rows(const mc_dwconv_args* a) {
@@ -1442,28 +1378,18 @@ extern "C" int mc_dwconv_bwd_data(const mc_dwconv_args* a, void* stream) {
     MC_CHECK(!p.dw_out || p.xw, "dwconv_bwd_data: the fused weight gradient (dw_out) is provided for the e-forming form (xw)");
     MC_CHECK(!(p.epi_x && p.stat_rows > 0) || p.stat_rows == mc_dwconv_bwd_data_stat_rows(a),
              "dwconv_bwd_data: stat_partials was sized for another configuration");
-    if (p.xw) {
-        hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)stream;
+    if (p.xw) {                                                        // (3x3 stride 2: mc_dwconv_bwd_data_xw_supported)
         MC_CHECK(mc_aligned16(p.epi_x) && mc_aligned16(p.xw), "dwconv_bwd_data (e from the block input): x / xw must be 16-byte aligned");
-        const bool t48 = p.c % 48 == 0 && p.c < 192;
-        if (p.cin <= 32) return t48 ? launch_march_bwd_s2_epi<3, 4, 12, 1, 1>(p, st) : launch_march_bwd_s2_epi<3, 4, 16, 1, 1>(p, st);
-        return t48 ? launch_march_bwd_s2_epi<3, 4, 12, 1, 2>(p, st) : launch_march_bwd_s2_epi<3, 4, 16, 1, 2>(p, st);
+        return march_bwd_s2_dispatch<true>(p, [&](auto cfg) {
+            using C = decltype(cfg);
+            if constexpr (C::K == 3) return p.cin <= 32 ? launch_march_bwd_s2<C, 1>(p, st) : launch_march_bwd_s2<C, 2>(p, st);
+            else return (int)MC_ERR_ARG;
+        });
     }
-    if (p.stride == 2 && p.epi_x) {
-        hipStream_t st = (hipStream_t)stream;
-        if (p.k == 3) {
-            if (p.c % 48 == 0 && p.c < 192) return launch_march_bwd_s2_epi<3, 4, 12, 1>(p, st);
-            return launch_march_bwd_s2_epi<3, 4, 16, 1>(p, st);
-        }
-        return launch_march_bwd_s2_epi<5, 2, 32, 2>(p, st);
-    }
-    if (p.stride == 2) {                                               // marching form
-        hipStream_t st = (hipStream_t)stream;
-        if (p.k == 3) {
-            if (p.c % 48 == 0 && p.c < 192) return launch_march_bwd_s2<3, 4, 12, 1>(p, st);
-            return launch_march_bwd_s2<3, 4, 16, 1>(p, st);
-        }
-        return launch_march_bwd_s2<5, 2, 32, 2>(p, st);
+    if (p.stride == 2) {                                               // marching form, with or without the epilogue
+        if (p.epi_x) return march_bwd_s2_dispatch<true>(p, [&](auto cfg) { return launch_march_bwd_s2<decltype(cfg)>(p, st); });
+        return march_bwd_s2_dispatch<false>(p, [&](auto cfg) { return launch_march_bwd_s2<decltype(cfg)>(p, st); });
     }
     long long total = (long long)p.n * p.h * p.w * (p.c / 8);
     int blocks = mc_div_up(total, 256);

@@ -1,5 +1,5 @@
-// Standalone micro-benchmark / phase profiler for the depthwise kernels (developer tool, not part of the library).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DMARCH_PROF] scripts/dwbench.hip -o /tmp/dwbench && /tmp/dwbench
+// Standalone micro-benchmark for the depthwise kernels (developer tool, not part of the library).
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/dwbench.hip -o /tmp/dwbench && /tmp/dwbench
 #include "../mammo_clip_amd/csrc/conv.hip"
 #include "../mammo_clip_amd/csrc/conv_lane.hip"
 #include <cstdio>
@@ -35,22 +35,12 @@ int main(int argc, char** argv) {
             a.pro_scale = pro ? sc : nullptr; a.pro_shift = pro ? sh : nullptr; a.stat_partials = pro ? part : nullptr;
             if (mc_dwconv_fwd(&a, nullptr)) { printf("err %s\n", mc_last_error()); return 1; }
             HC(hipDeviceSynchronize());
-#ifdef MARCH_PROF
-            unsigned long long z[8] = {0}; HC(hipMemcpyToSymbol(HIP_SYMBOL(g_march_prof), z, sizeof(z)));
-#endif
             HC(hipEventRecord(e0));
             const int it = 5;
             for (int i = 0; i < it; ++i) mc_dwconv_fwd(&a, nullptr);
             HC(hipEventRecord(e1)); HC(hipEventSynchronize(e1));
             float ms; HC(hipEventElapsedTime(&ms, e0, e1)); ms /= it;
-            printf("fwd k%ds%d c=%4d %3dx%3d pro=%d  %7.3f ms %7.1f GB/s", s.k, s.s, s.c, s.h, s.w, pro, ms, bytes / ms / 1e6);
-#ifdef MARCH_PROF
-            HC(hipMemcpyFromSymbol(z, HIP_SYMBOL(g_march_prof), sizeof(z)));
-            double tot = (double)(z[0] + z[1] + z[2] + z[3] + z[4]);
-            printf("  | bar1 %4.1f%% store %4.1f%% bar2 %4.1f%% issue %4.1f%% compute %4.1f%%  blocks %llu cyc/blk %.0f", 100 * z[0] / tot,
-                   100 * z[1] / tot, 100 * z[2] / tot, 100 * z[3] / tot, 100 * z[4] / tot, z[5], tot / (z[5] ? z[5] : 1));
-#endif
-            printf("\n");
+            printf("fwd k%ds%d c=%4d %3dx%3d pro=%d  %7.3f ms %7.1f GB/s\n", s.k, s.s, s.c, s.h, s.w, pro, ms, bytes / ms / 1e6);
         }
         {   // weight gradient (x with prologue, dy = y buffer)
             a.pro_scale = sc; a.pro_shift = sh; a.stat_partials = nullptr; a.dy = y; a.out = w;

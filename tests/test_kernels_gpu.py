@@ -1506,6 +1506,110 @@ def test_dwconv_s2_dgrad_with_bn_backward_epilogue(k, n, h, w, c, pad):
     check(db, db_ref, 1e-2, "dbeta")
 
 
+def _bn_stats_of(e, c, seed):
+    """BatchNorm statistics block of e [rows, c] with seeded gamma / beta (as the epilogue tests above build it)"""
+    gamma, beta = rnd(c, seed=seed, dtype=torch.float32) * 0.2 + 1.0, rnd(c, seed=seed + 1, dtype=torch.float32) * 0.1
+    ef = e.float()
+    mean, var = ef.mean(0), ef.var(0, unbiased=False)
+    st = ops.BNStats()
+    st.mean, st.invstd = mean.contiguous(), (var + 1e-3).rsqrt().contiguous()
+    st.scale = (gamma * st.invstd).contiguous()
+    st.shift = (beta - mean * st.scale).contiguous()
+    st.count = float(e.shape[0])
+    return st
+
+
+def _check_bn_backward_epilogue(dz, part, da_ref, e, st, what):
+    """dZ0 = dA0 * silu'(e * scale + shift) and the two BatchNorm-backward sums (sum dZ0, sum dZ0 * xhat0) against fp32 torch:
+    da_ref [rows, c] is autograd's data gradient"""
+    ef = e.float()
+    z = ef * st.scale + st.shift
+    sg = torch.sigmoid(z)
+    dz_ref = da_ref * (sg * (1 + z * (1 - sg)))
+    check(dz, dz_ref, 1.5e-2, what + ": dZ0")
+    sums = part.double().sum(0)
+    xhat = ((ef - st.mean) * st.invstd).double()
+    check(sums[0].float(), dz_ref.double().sum(0).float(), 1e-2, what + ": sum dZ0 (dbeta)")
+    check(sums[1].float(), (dz_ref.double() * xhat).sum(0).float(), 1e-2, what + ": sum dZ0 * xhat0 (dgamma)")
+
+
+@pytest.mark.parametrize("k,s,pad,c", [(3, 1, (1, 1, 1, 1), 24), (3, 1, (1, 1, 1, 1), 72), (3, 2, (1, 1, 0, 1), 48), (5, 2, (2, 2, 1, 2), 40)])
+def test_dwconv_marching_several_items_per_workgroup(k, s, pad, c):
+    """The marching kernels' persistent loop past its first item: many small images, so that every workgroup owns two or more
+    items (asserted through the work split: stat rows = workgroups per channel tile <= n / 2 <= items / 2) of several staged
+    blocks each (h = 20).  That exercises the hand-over between items (accumulators and output pointer reset at block 0) and
+    the prefetch of the next item's first block while the current item finishes.  Forward with prologue and statistics, weight
+    gradient, stride-1 data gradient with the BatchNorm-backward epilogue, stride-2 data gradient with and without it; 6-lane
+    tiles (c = 24), a ragged second 64-channel tile (c = 72), 48-channel tiles and the 5x5 form.  Reference: fp32 torch conv2d +
+    autograd on the 16-bit-rounded operands; tolerances of test_dwconv_fwd / test_dwconv_bwd and of the epilogue tests.  (The
+    stride-2 pads are the static "same" pads of a 20 x 9 map: odd width symmetric, even height one-sided.)"""
+    import ctypes as C
+    n, h, w = 1000, 20, 9
+    Lh = L.load()
+    x = rnd(n, h, w, c, seed=51)
+    wt = rnd(c, 1, k, k, seed=52, dtype=torch.float32) * 0.3
+    st = _bn_stats_of(x.view(-1, c), c, 53)
+    pro = (st.scale, st.shift)
+    a = F.silu(x.float() * pro[0] + pro[1]).to(BF).float().permute(0, 3, 1, 2).requires_grad_(True)
+    wr = wt.clone().requires_grad_(True)
+    ref = F.conv2d(F.pad(a, pad), wr, None, s, 0, 1, c)
+    oh, ow = ref.shape[2], ref.shape[3]
+    dy = rnd(n, oh, ow, c, seed=54)
+    ref.backward(dy.float().permute(0, 3, 1, 2))
+    w_kkc = wt.view(c, k * k).t().contiguous()
+    geo = (n, h, w, c, k, s, pad[0], pad[2], oh, ow)
+    old = Lh.mc_dwconv_set_lane_mode(0)
+    try:
+        assert Lh.mc_dwconv_stat_rows(C.byref(ops._dw_args(*geo))) <= n // 2, "every workgroup needs a second item"
+        y, part = ops.dwconv_fwd(x.view(-1, c), w_kkc, *geo, pro=pro, stats=True)
+        check(y.view(n, oh, ow, c).permute(0, 3, 1, 2), ref.detach(), 1e-2, "dw fwd")
+        sums, yf = part.double().sum(0), y.float().double()
+        check(sums[0].float(), yf.sum(0).float(), 1e-4, "dw colsum")
+        check(sums[1].float(), (yf * yf).sum(0).float(), 1e-4, "dw colsumsq")
+        dw = ops.dwconv_bwd_weight(x.view(-1, c), dy.view(-1, c), *geo, pro=pro)
+        check(dw.t().reshape(c, 1, k, k), wr.grad, 2e-3, "dw bwd weight")
+        da_ref = a.grad.permute(0, 2, 3, 1).reshape(-1, c)
+        if s == 1:
+            w_flip = wt.flip(2, 3).reshape(c, k * k).t().contiguous()
+            dz, part = ops.dwconv_bwd_data(dy.view(-1, c), w_kkc, *geo, w_kkc_flipped=w_flip, epi=(x.view(-1, c), st))
+            assert part.shape[0] <= n // 2
+            _check_bn_backward_epilogue(dz, part, da_ref, x.view(-1, c), st, "stride-1 dgrad")
+        else:
+            assert Lh.mc_dwconv_bwd_data_stat_rows(C.byref(ops._dw_args(*geo))) <= n // 2, "every workgroup needs a second item"
+            dx = ops.dwconv_bwd_data(dy.view(-1, c), w_kkc, *geo)
+            check(dx, da_ref, 1e-2, "stride-2 dgrad")
+            dz, part = ops.dwconv_bwd_data(dy.view(-1, c), w_kkc, *geo, epi=(x.view(-1, c), st))
+            _check_bn_backward_epilogue(dz, part, da_ref, x.view(-1, c), st, "stride-2 dgrad")
+    finally:
+        Lh.mc_dwconv_set_lane_mode(old)
+
+
+@pytest.mark.parametrize("k,n,h,w,c,pad", [(3, 2, 140, 70, 72, (0, 1)), (5, 1, 141, 71, 40, (1, 2))])
+def test_dwconv_s2_dgrad_row_segments_and_strips(k, n, h, w, c, pad):
+    """Stride-2 data gradient, plain and with the BatchNorm-backward epilogue, on one tall and wide map: several column strips
+    and several row segments per image (asserted through mc_dwconv_bwd_data_plan), so neighbouring segments meet across their
+    D - 1 halo rows of dy and strips across their halo columns.  Reference: autograd of the fp32 torch conv2d."""
+    import ctypes as C
+    pl, pt = pad
+    oh, ow = (h + 1) // 2, (w + 1) // 2
+    plan = (C.c_int * 4)()
+    assert L.load().mc_dwconv_bwd_data_plan(C.byref(ops._dw_args(n, h, w, c, k, 2, pl, pt, oh, ow)), plan) > 0
+    assert plan[0] > 1 and plan[1] > 1, f"strips {plan[0]}, segments {plan[1]}"
+    e = rnd(n * h * w, c, seed=61)
+    dd = rnd(n * oh * ow, c, seed=62)
+    wt = rnd(c, 1, k, k, seed=63, dtype=torch.float32) * 0.3
+    st = _bn_stats_of(e, c, 64)
+    a = torch.zeros(n, c, h, w, device=DEV, requires_grad=True)
+    full = (pl, (ow - 1) * 2 + k - w - pl, pt, (oh - 1) * 2 + k - h - pt)
+    F.conv2d(F.pad(a, full), wt, None, 2, 0, 1, c).backward(dd.float().view(n, oh, ow, c).permute(0, 3, 1, 2))
+    da_ref = a.grad.permute(0, 2, 3, 1).reshape(-1, c)
+    w_kkc = wt.view(c, k * k).t().contiguous()
+    dx = ops.dwconv_bwd_data(dd, w_kkc, n, h, w, c, k, 2, pl, pt, oh, ow)
+    check(dx, da_ref, 1e-2, "stride-2 dgrad")
+    dz, part = ops.dwconv_bwd_data(dd, w_kkc, n, h, w, c, k, 2, pl, pt, oh, ow, epi=(e, st))
+    _check_bn_backward_epilogue(dz, part, da_ref, e, st, "stride-2 dgrad")
+
+
 @pytest.mark.parametrize("n_img,hw,cexp,cout", [(4, 4096, 240, 40), (3, 6016, 144, 40), (5, 2048, 24, 24), (2, 16384, 48, 24),  # (the model fuses from 192 channels up)
                                                 (6, 1600, 96, 16), (2, 8192, 256, 64), (2, 4096, 144, 24), (3, 2736, 208, 32), (2, 4112, 176, 128)])
 def test_proj_dgrad_with_se_and_bn1_backward_epilogues(n_img, hw, cexp, cout):
