@@ -650,6 +650,36 @@ int mc_adamw_step_ls(const mc_adamw_tensor* tensors, int n_tensors, double lr, d
                      double weight_decay, long long step, const float* found_inf, const float* skipped, void* stream);
 int mc_loss_scale_update(float* state, float* opt_skipped, double growth_factor, double backoff_factor, int growth_interval,
                          int dynamic, void* stream);
+/* Global L2 norm of the gradients and clipping by it, on the device with no host read [ref: the downstream loops call
+ * torch.nn.utils.clip_grad_norm_, Detectors/experiments.py:103].  Only .grad and .numel of the list are read; one workgroup
+ * owns one 16384-element chunk of one tensor and writes that chunk's fp64 sum of squares to partials[chunk index of the
+ * call]; a last one-workgroup launch adds the partials in a fixed order.  No floating-point atomics: the result is the same
+ * bit for bit on every run and stream.
+ *   out2[0] = (float)sqrt(sum g^2), the sum and its terms in fp64 (gradients of 1e-25 or 1e25 neither vanish nor overflow)
+ *   out2[1] = min(1, max_norm / (out2[0] + 1e-6)), formed in fp32 from the ROUNDED norm the way torch forms the python
+ *             expression `max_norm / tensor`: the correctly rounded reciprocal times max_norm.  A nan norm gives a nan
+ *             coefficient (torch.clamp(nan, max=1)), max_norm = inf gives exactly 1, an empty list gives norm 0.
+ * max_norm must be > 0 (inf allowed; nan is refused).  Every argument is checked before the first launch.
+ *   mc_grad_norm_partials     : host arithmetic only: the doubles of workspace the list needs, sum of ceil(numel / 16384);
+ *                               -1 on a bad list (negative n_tensors or numel, NULL list with n_tensors > 0)
+ *   mc_grad_norm              : norm and coefficient of the gradients as they are; n_partials = capacity of `partials`
+ *   mc_grads_unscale_norm_dev : mc_grads_unscale_dev whose workgroups also sum the squares of the values they STORE (the
+ *                               fp32-rounded unscaled gradients) with the same per-chunk code as mc_grad_norm: gradients and
+ *                               out2 are bit-equal to mc_grads_unscale_dev followed by mc_grad_norm, in one pass
+ *   mc_grads_scale_dev        : grad *= *coef in place (one fp32 product per element, no reciprocal): the clip for optimizers
+ *                               other than the HIP AdamW
+ *   mc_adamw_step_clip        : mc_adamw_step (found_inf = skipped = NULL) or mc_adamw_step_ls (both set) that multiplies
+ *                               every gradient by *grad_coef as it loads it -- one fp32 rounding, the product Tensor.mul_
+ *                               would have stored.  The gradients in memory are NOT rewritten.  grad_coef is required. */
+long long mc_grad_norm_partials(const mc_adamw_tensor* tensors, int n_tensors);
+int mc_grad_norm(const mc_adamw_tensor* tensors, int n_tensors, double* partials, long long n_partials, float max_norm,
+                 float* out2, void* stream);
+int mc_grads_unscale_norm_dev(const mc_adamw_tensor* tensors, int n_tensors, const float* scale_dev, float* found_inf,
+                              double* partials, long long n_partials, float max_norm, float* out2, void* stream);
+int mc_grads_scale_dev(const mc_adamw_tensor* tensors, int n_tensors, const float* coef, void* stream);
+int mc_adamw_step_clip(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, long long step, const float* grad_coef, const float* found_inf,
+                       const float* skipped, void* stream);
 
 #ifdef __cplusplus
 }

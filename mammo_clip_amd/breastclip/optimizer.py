@@ -84,11 +84,12 @@ class AdamW(torch.optim.Optimizer):
         return plan
 
     @torch.no_grad()
-    def step_loss_scaled(self, scaler):
+    def step_loss_scaled(self, scaler, grad_coef=None):
         """``step()`` under an ``engine.LossScaler`` without a host sync: the kernel reads the scaler's non-finite flag and
         does nothing on a bad step (GradScaler.step() would not call optimizer.step()); its bias corrections use the
         number of APPLIED steps = attempted steps (counted on the host) - skipped steps (counted on the device, in a tensor
-        this optimizer owns: it survives a change of scaler).  Returns that counter for ``scaler.update``."""
+        this optimizer owns: it survives a change of scaler).  Returns that counter for ``scaler.update``.
+        ``grad_coef``: as in ``step``."""
         dev = self.param_groups[0]["params"][0].device
         if getattr(self, "_ls_skipped", None) is None or self._ls_skipped.device != dev:
             self._fold_skipped()                           # (a counter on another device: fold it into the host counts)
@@ -96,7 +97,7 @@ class AdamW(torch.optim.Optimizer):
         st = scaler.state(dev)
         self._ls = (st.data_ptr() + 4 * scaler._FLAG, self._ls_skipped.data_ptr())
         try:
-            self.step()
+            self.step(grad_coef=grad_coef)
         finally:
             self._ls = None
         return self._ls_skipped
@@ -107,8 +108,13 @@ class AdamW(torch.optim.Optimizer):
         self._ls_skipped = None
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, grad_coef=None):
+        """``grad_coef``: a 1-element fp32 device tensor (the clip coefficient of ``ops.grad_norm_coef``); every gradient is
+        multiplied by it as the kernel loads it (``mc_adamw_step_clip``), ``p.grad`` itself is left as it is."""
         loss = None
+        if grad_coef is not None and not (torch.is_tensor(grad_coef) and grad_coef.is_cuda and grad_coef.dtype == torch.float32
+                                          and grad_coef.numel() >= 1):
+            raise L.MammoClipHipError("AdamW: grad_coef must be an fp32 tensor on the GPU (the HIP kernel is the only path)")
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
@@ -140,7 +146,10 @@ class AdamW(torch.optim.Optimizer):
             stream = torch.cuda.current_stream().cuda_stream
             hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
             ls = getattr(self, "_ls", None)
-            entry, tail = ("mc_adamw_step_ls", (ls[0], ls[1], stream)) if ls else ("mc_adamw_step", (stream,))
+            if grad_coef is not None:
+                entry, tail = "mc_adamw_step_clip", (grad_coef.data_ptr(), ls[0] if ls else None, ls[1] if ls else None, stream)
+            else:
+                entry, tail = ("mc_adamw_step_ls", (ls[0], ls[1], stream)) if ls else ("mc_adamw_step", (stream,))
             if min(steps) == max(steps):
                 L.call(entry, arr, len(params), *hyper, steps[0], *tail)
             else:                                             # parameters that joined later: one launch set per step count

@@ -49,8 +49,22 @@ struct AdamLs {
     const float* skipped;      // steps skipped so far (float counter)
     double lr, beta1, beta2;
     long long step;
+    const float* grad_coef;    // CLIP only: the clip coefficient of mc_grad_norm, a device scalar
 };
 
+// g * c rounded once to fp32, the value torch.Tensor.mul_ would have stored.  Written as the instruction: under
+// -ffp-contract=fast a C++ product would be fused into the (g - m) and g * g that consume it, which is another rounding.
+__device__ __forceinline__ float mul_rn(float g, float c) {
+    asm("v_mul_f32 %0, %1, %0" : "+v"(g) : "s"(c));     // c is uniform: a scalar operand, the product replaces g in place
+    return g;
+}
+__device__ __forceinline__ void mul_rn4(float4& g, float c) {
+    g.x = mul_rn(g.x, c); g.y = mul_rn(g.y, c); g.z = mul_rn(g.z, c); g.w = mul_rn(g.w, c);
+}
+
+// CLIP: every gradient is multiplied by *ls.grad_coef as it is loaded (gradient-norm clipping without rewriting the
+// gradients in memory); CLIP = false is the kernel as it was.
+template <bool CLIP>
 __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, AdamScalars s, AdamLs ls) {
     if (ls.found_inf) {
         if (*ls.found_inf != 0.f) return;                              // (uniform: the whole grid leaves)
@@ -65,6 +79,7 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
         s.step_size = s_dev[0];
         s.inv_bc2_sqrt = s_dev[1];
     }
+    const float c = CLIP ? *ls.grad_coef : 1.f;
     int t = 0;
     const int blk = blockIdx.x;
     while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;       // uniform scan, <= PACK scalar compares
@@ -87,6 +102,7 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
             float4 G0 = *(const float4*)(g + i), G1 = *(const float4*)(g + i + 1024);
             float4 M0 = *(const float4*)(m + i), M1 = *(const float4*)(m + i + 1024);
             float4 V0 = *(const float4*)(v + i), V1 = *(const float4*)(v + i + 1024);
+            if (CLIP) { mul_rn4(G0, c); mul_rn4(G1, c); }
             adamw1(P0.x, G0.x, M0.x, V0.x, s); adamw1(P0.y, G0.y, M0.y, V0.y, s);
             adamw1(P0.z, G0.z, M0.z, V0.z, s); adamw1(P0.w, G0.w, M0.w, V0.w, s);
             adamw1(P1.x, G1.x, M1.x, V1.x, s); adamw1(P1.y, G1.y, M1.y, V1.y, s);
@@ -102,6 +118,7 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
         for (; i + 3 < len; i += 1024) {
             float4 P0 = *(const float4*)(p + i), G0 = *(const float4*)(g + i);
             float4 M0 = *(const float4*)(m + i), V0 = *(const float4*)(v + i);
+            if (CLIP) mul_rn4(G0, c);
             adamw1(P0.x, G0.x, M0.x, V0.x, s); adamw1(P0.y, G0.y, M0.y, V0.y, s);
             adamw1(P0.z, G0.z, M0.z, V0.z, s); adamw1(P0.w, G0.w, M0.w, V0.w, s);
             *(float4*)(p + i) = P0; *(float4*)(m + i) = M0; *(float4*)(v + i) = V0;
@@ -112,14 +129,14 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
         const int j = done + threadIdx.x;
         if (j < len) {
             float P = p[j], M = m[j], V = v[j];
-            adamw1(P, g[j], M, V, s);
+            adamw1(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
             p[j] = P; m[j] = M; v[j] = V;
             if (img) img[j] = f2bf(P);
         }
     } else {
         for (int j = threadIdx.x; j < len; j += 256) {
             float P = p[j], M = m[j], V = v[j];
-            adamw1(P, g[j], M, V, s);
+            adamw1(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
             p[j] = P; m[j] = M; v[j] = V;
             if (img) img[j] = f2bf(P);
         }
@@ -138,9 +155,71 @@ struct UnscalePack {
 // torch.isfinite's answer: +-FLT_MAX is a finite gradient, inf and nan (every compare with nan is false) are not
 __device__ __forceinline__ bool nonfinite(float v) { return !(fabsf(v) <= FLT_MAX); }
 
-__global__ void __launch_bounds__(256) grads_unscale_k(UnscalePack pk, int count, float inv_scale, const float* __restrict__ scale_dev,
-                                                       float* __restrict__ found_inf) {
-    if (scale_dev) inv_scale = 1.0f / *scale_dev;                       // the dynamic scale lives on the device (no host sync)
+// One pass of a workgroup over its chunk, shared by every gradient kernel below.  STORE: g = g * mul in place, `bad` set on
+// a non-finite product.  NORM: returns this lane's sum of v * v over the values it kept (the stored ones under STORE), in
+// fp64 -- the product of two fp32 values is exact there, 1e-25 and 1e25 neither underflow nor overflow, and the lane adds
+// its terms in index order, so the sum depends on the chunk's address and length alone (never on the kernel around it).
+template <bool STORE, bool NORM>
+__device__ __forceinline__ float pass1(float v, float mul, bool& bad, double& acc) {
+    if (STORE) { v *= mul; bad |= nonfinite(v); }
+    if (NORM) acc += (double)v * (double)v;
+    return v;
+}
+
+template <bool STORE, bool NORM>
+__device__ __forceinline__ double chunk_pass(float* __restrict__ g, int len, float mul, bool& bad) {
+    double acc = 0.0;
+    int i = threadIdx.x * 4;
+    if ((((uintptr_t)g) & 15) == 0) {
+        // 4 float4 in flight per lane before the first use (one load at a time leaves the pass latency-bound at less than
+        // half of the HBM rate); the values are consumed in index order either way, so the lane's sum does not change
+        for (; i + 3 * 1024 + 3 < len; i += 4096) {
+            float4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = *(const float4*)(g + i + u * 1024);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                v[u].x = pass1<STORE, NORM>(v[u].x, mul, bad, acc); v[u].y = pass1<STORE, NORM>(v[u].y, mul, bad, acc);
+                v[u].z = pass1<STORE, NORM>(v[u].z, mul, bad, acc); v[u].w = pass1<STORE, NORM>(v[u].w, mul, bad, acc);
+                if (STORE) *(float4*)(g + i + u * 1024) = v[u];
+            }
+        }
+        for (; i + 3 < len; i += 1024) {
+            float4 v = *(const float4*)(g + i);
+            v.x = pass1<STORE, NORM>(v.x, mul, bad, acc); v.y = pass1<STORE, NORM>(v.y, mul, bad, acc);
+            v.z = pass1<STORE, NORM>(v.z, mul, bad, acc); v.w = pass1<STORE, NORM>(v.w, mul, bad, acc);
+            if (STORE) *(float4*)(g + i) = v;
+        }
+        const int j = (len & ~3) + threadIdx.x;
+        if (j < len) { const float v = pass1<STORE, NORM>(g[j], mul, bad, acc); if (STORE) g[j] = v; }
+    } else {
+        for (int j = threadIdx.x; j < len; j += 256) { const float v = pass1<STORE, NORM>(g[j], mul, bad, acc); if (STORE) g[j] = v; }
+    }
+    return acc;
+}
+
+// sum over the 256 lanes of a workgroup in a fixed order (a tree over LDS: no atomics, no dependence on wave timing)
+__device__ __forceinline__ double block_sum256(double v, double* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// <STORE, NORM> = <1, 0>: the unscale (mul = inv_scale or 1 / *scale_dev) and the in-place clip (mul = *mul_dev, a plain
+// product, no flag); <1, 1>: the unscale that also writes its chunk's sum of squares; <0, 1>: the sum of squares alone.
+// partials: one double per workgroup, at this launch's running chunk offset of the whole call.
+template <bool STORE, bool NORM>
+__global__ void __launch_bounds__(256) grads_pass_k(UnscalePack pk, int count, float mul, const float* __restrict__ scale_dev,
+                                                    const float* __restrict__ mul_dev, float* __restrict__ found_inf,
+                                                    double* __restrict__ partials) {
+    if (STORE) {
+        if (scale_dev) mul = 1.0f / *scale_dev;                         // the dynamic scale lives on the device (no host sync)
+        else if (mul_dev) mul = *mul_dev;
+    }
     int t = 0;
     const int blk = blockIdx.x;
     while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;
@@ -149,20 +228,32 @@ __global__ void __launch_bounds__(256) grads_unscale_k(UnscalePack pk, int count
     const long long left = pk.n[t] - base;
     const int len = left < CHUNK ? (int)left : CHUNK;
     bool bad = false;
-    int i = threadIdx.x * 4;
-    if ((((uintptr_t)g) & 15) == 0) {
-        for (; i + 3 < len; i += 1024) {
-            float4 v = *(const float4*)(g + i);
-            v.x *= inv_scale; v.y *= inv_scale; v.z *= inv_scale; v.w *= inv_scale;
-            bad |= nonfinite(v.x) || nonfinite(v.y) || nonfinite(v.z) || nonfinite(v.w);
-            *(float4*)(g + i) = v;
-        }
-        const int j = (len & ~3) + threadIdx.x;
-        if (j < len) { const float v = g[j] * inv_scale; bad |= nonfinite(v); g[j] = v; }
-    } else {
-        for (int j = threadIdx.x; j < len; j += 256) { const float v = g[j] * inv_scale; bad |= nonfinite(v); g[j] = v; }
+    const double acc = chunk_pass<STORE, NORM>(g, len, mul, bad);
+    if (STORE && bad && found_inf) *found_inf = 1.0f;          // (every writer stores the same value)
+    if (NORM) {
+        __shared__ double sh[256];
+        const double tot = block_sum256(acc, sh);
+        if (threadIdx.x == 0) partials[blk] = tot;
     }
-    if (bad) *found_inf = 1.0f;          // (every writer stores the same value)
+}
+
+// total norm and clip coefficient from the per-chunk sums: one workgroup, thread-strided pass then the fixed tree.
+// out[0] = (float)sqrt(sum); out[1] = min(1, max_norm / (out[0] + 1e-6)) in fp32 from the ROUNDED norm, with the quotient
+// formed the way torch forms `max_norm / tensor` (Tensor.__rtruediv__): the correctly rounded reciprocal times max_norm,
+// two roundings.  (float)(1.0 / (double)d) IS the correctly rounded fp32 reciprocal: 53 >= 2 * 24 + 2 bits.  A nan norm
+// gives a nan coefficient (every compare with nan is false), an infinite max_norm gives 1.
+__global__ void __launch_bounds__(256) grad_norm_finish_k(const double* __restrict__ partials, long long n, float max_norm,
+                                                          float* __restrict__ out) {
+    __shared__ double sh[256];
+    double acc = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 256) acc += partials[i];
+    const double tot = block_sum256(acc, sh);
+    if (threadIdx.x == 0) {
+        const float nrm = (float)sqrt(tot);
+        const float c = mul_rn((float)(1.0 / (double)(nrm + 1e-6f)), max_norm);
+        out[0] = nrm;
+        out[1] = c > 1.0f ? 1.0f : c;
+    }
 }
 
 // GradScaler.update() on the device [ref: trainer_ddp.py:303]: state = {scale, clean steps in a row, found_inf flag of the
@@ -189,17 +280,71 @@ __global__ void loss_scale_update_k(float* __restrict__ st, float* __restrict__ 
     st[2] = 0.f;
 }
 
-int grads_unscale_impl(const mc_adamw_tensor* tensors, int n_tensors, float inv_scale, const float* scale_dev, float* found_inf, void* stream);
+enum GradPass { GP_UNSCALE, GP_UNSCALE_NORM, GP_NORM };
+int grads_pass_impl(GradPass mode, const mc_adamw_tensor* tensors, int n_tensors, float mul, const float* scale_dev,
+                    const float* mul_dev, float* found_inf, double* partials, void* stream);
+int grad_norm_finish(const double* partials, long long n, float max_norm, float* out2, void* stream);
+int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
+               long long step, const float* grad_coef, const float* found_inf, const float* skipped, void* stream);
+
+// chunks (= doubles of norm workspace) of a gradient list, -1 on a bad one; need_grad: every non-empty tensor has a pointer
+long long list_chunks(const mc_adamw_tensor* tensors, int n_tensors, bool need_grad) {
+    if (n_tensors < 0 || (!tensors && n_tensors > 0)) return -1;
+    long long tot = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (tensors[i].numel < 0 || (need_grad && tensors[i].numel > 0 && !tensors[i].grad)) return -1;
+        tot += (tensors[i].numel + CHUNK - 1) / CHUNK;
+    }
+    return tot;
+}
 
 }  // namespace
 
 extern "C" int mc_grads_unscale(const mc_adamw_tensor* tensors, int n_tensors, float inv_scale, float* found_inf, void* stream) {
-    return grads_unscale_impl(tensors, n_tensors, inv_scale, nullptr, found_inf, stream);
+    MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0) && found_inf, "grads_unscale: bad arguments");
+    return grads_pass_impl(GP_UNSCALE, tensors, n_tensors, inv_scale, nullptr, nullptr, found_inf, nullptr, stream);
 }
 
 extern "C" int mc_grads_unscale_dev(const mc_adamw_tensor* tensors, int n_tensors, const float* scale_dev, float* found_inf, void* stream) {
     MC_CHECK(scale_dev, "grads_unscale_dev: null scale");
-    return grads_unscale_impl(tensors, n_tensors, 1.0f, scale_dev, found_inf, stream);
+    MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0) && found_inf, "grads_unscale: bad arguments");
+    return grads_pass_impl(GP_UNSCALE, tensors, n_tensors, 1.0f, scale_dev, nullptr, found_inf, nullptr, stream);
+}
+
+extern "C" long long mc_grad_norm_partials(const mc_adamw_tensor* tensors, int n_tensors) {
+    const long long need = list_chunks(tensors, n_tensors, false);
+    if (need < 0) mc_set_error("grad_norm_partials: bad tensor list");
+    return need;
+}
+
+extern "C" int mc_grad_norm(const mc_adamw_tensor* tensors, int n_tensors, double* partials, long long n_partials, float max_norm,
+                            float* out2, void* stream) {
+    const long long need = list_chunks(tensors, n_tensors, true);
+    MC_CHECK(need >= 0, "grad_norm: bad tensor list");
+    MC_CHECK(out2, "grad_norm: null output");
+    MC_CHECK(max_norm > 0.f, "grad_norm: max_norm must be positive (inf: the norm alone)");         // (false for nan)
+    MC_CHECK(n_partials >= need && (partials || need == 0), "grad_norm: partials workspace too small");
+    int r = grads_pass_impl(GP_NORM, tensors, n_tensors, 1.0f, nullptr, nullptr, nullptr, partials, stream);
+    if (r != MC_OK) return r;
+    return grad_norm_finish(partials, need, max_norm, out2, stream);
+}
+
+extern "C" int mc_grads_unscale_norm_dev(const mc_adamw_tensor* tensors, int n_tensors, const float* scale_dev, float* found_inf,
+                                         double* partials, long long n_partials, float max_norm, float* out2, void* stream) {
+    const long long need = list_chunks(tensors, n_tensors, true);
+    MC_CHECK(need >= 0, "grads_unscale_norm_dev: bad tensor list");
+    MC_CHECK(scale_dev && found_inf && out2, "grads_unscale_norm_dev: null scale, flag or output");
+    MC_CHECK(max_norm > 0.f, "grads_unscale_norm_dev: max_norm must be positive (inf: the norm alone)");
+    MC_CHECK(n_partials >= need && (partials || need == 0), "grads_unscale_norm_dev: partials workspace too small");
+    int r = grads_pass_impl(GP_UNSCALE_NORM, tensors, n_tensors, 1.0f, scale_dev, nullptr, found_inf, partials, stream);
+    if (r != MC_OK) return r;
+    return grad_norm_finish(partials, need, max_norm, out2, stream);
+}
+
+extern "C" int mc_grads_scale_dev(const mc_adamw_tensor* tensors, int n_tensors, const float* coef, void* stream) {
+    MC_CHECK(list_chunks(tensors, n_tensors, true) >= 0, "grads_scale_dev: bad tensor list");
+    MC_CHECK(coef, "grads_scale_dev: null coefficient");
+    return grads_pass_impl(GP_UNSCALE, tensors, n_tensors, 1.0f, nullptr, coef, nullptr, nullptr, stream);
 }
 
 extern "C" int mc_loss_scale_update(float* state, float* opt_skipped, double growth_factor, double backoff_factor, int growth_interval,
@@ -212,15 +357,19 @@ extern "C" int mc_loss_scale_update(float* state, float* opt_skipped, double gro
 }
 
 namespace {
-int grads_unscale_impl(const mc_adamw_tensor* tensors, int n_tensors, float inv_scale, const float* scale_dev, float* found_inf, void* stream) {
-    MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0) && found_inf, "grads_unscale: bad arguments");
+int grads_pass_impl(GradPass mode, const mc_adamw_tensor* tensors, int n_tensors, float mul, const float* scale_dev,
+                    const float* mul_dev, float* found_inf, double* partials, void* stream) {
     UnscalePack pk;
     int cnt = 0, chunks = 0;
+    long long chunk_base = 0;                // chunks of the launches before this one: where its partials start
     auto flush = [&]() -> int {
         if (cnt == 0) return MC_OK;
         pk.first_chunk[cnt] = chunks;
-        hipLaunchKernelGGL(grads_unscale_k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, inv_scale, scale_dev, found_inf);
+        double* part = partials ? partials + chunk_base : nullptr;
+        auto k = mode == GP_UNSCALE ? grads_pass_k<true, false> : mode == GP_UNSCALE_NORM ? grads_pass_k<true, true> : grads_pass_k<false, true>;
+        hipLaunchKernelGGL(k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, mul, scale_dev, mul_dev, found_inf, part);
         MC_LAUNCH_CHECK();
+        chunk_base += chunks;
         cnt = 0; chunks = 0;
         return MC_OK;
     };
@@ -241,25 +390,36 @@ int grads_unscale_impl(const mc_adamw_tensor* tensors, int n_tensors, float inv_
     return flush();
 }
 
-int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
-               long long step, const float* found_inf, const float* skipped, void* stream);
+int grad_norm_finish(const double* partials, long long n, float max_norm, float* out2, void* stream) {
+    hipLaunchKernelGGL(grad_norm_finish_k, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out2);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
 }  // namespace
 
 extern "C" int mc_adamw_step(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
                              double eps, double weight_decay, long long step, void* stream) {
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, stream);
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mc_adamw_step_ls(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
                                 double eps, double weight_decay, long long step, const float* found_inf, const float* skipped,
                                 void* stream) {
     MC_CHECK(found_inf && skipped, "adamw_step_ls: null loss-scale state");
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, found_inf, skipped, stream);
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, found_inf, skipped, stream);
+}
+
+extern "C" int mc_adamw_step_clip(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
+                                  double eps, double weight_decay, long long step, const float* grad_coef, const float* found_inf,
+                                  const float* skipped, void* stream) {
+    MC_CHECK(grad_coef, "adamw_step_clip: null grad_coef");
+    MC_CHECK((found_inf == nullptr) == (skipped == nullptr), "adamw_step_clip: found_inf and skipped are both null or both set");
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, stream);
 }
 
 namespace {
 int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
-               long long step, const float* found_inf, const float* skipped, void* stream) {
+               long long step, const float* grad_coef, const float* found_inf, const float* skipped, void* stream) {
     MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0), "adamw: bad tensor list");
     MC_CHECK(step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adamw: bad hyper-parameters");
     // scalars are derived in double like torch does on the host (1 - 0.999 in fp32 is already 1.3e-5 off)
@@ -273,12 +433,13 @@ int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double 
     s.eps = (float)eps;
     AdamLs ls;
     ls.found_inf = found_inf; ls.skipped = skipped; ls.lr = lr; ls.beta1 = beta1; ls.beta2 = beta2; ls.step = step;
+    ls.grad_coef = grad_coef;
     AdamPack pk;
     int cnt = 0, chunks = 0;
     auto flush = [&]() -> int {
         if (cnt == 0) return MC_OK;
         pk.first_chunk[cnt] = chunks;
-        hipLaunchKernelGGL(adamw_multi_k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, s, ls);
+        hipLaunchKernelGGL(grad_coef ? adamw_multi_k<true> : adamw_multi_k<false>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, s, ls);
         MC_LAUNCH_CHECK();
         cnt = 0; chunks = 0;
         return MC_OK;

@@ -165,27 +165,26 @@ class LossScaler:
 
     # ---- the three launches of a loss-scaled optimizer step
     def _grad_table(self, params):
-        ps = [p for p in params if p.grad is not None]
-        arr = (L.AdamwTensor * max(len(ps), 1))()
-        keep = []
-        for a, p in zip(arr, ps):
-            g = p.grad
-            if not g.is_contiguous() or g.dtype != torch.float32:
-                raise L.MammoClipHipError("LossScaler: parameter gradients must be dense contiguous fp32 tensors")
-            keep.append(g)
-            a.grad, a.numel = g.data_ptr(), g.numel()
-        return ps, arr, keep
+        return ops.grad_table(params, "LossScaler")
 
-    def unscale_(self, params, sync=False):
+    def unscale_(self, params, sync=False, clip=None):
         """grad *= 1 / scale for every parameter gradient (one multi-tensor launch per 40 tensors), the non-finite flag goes
-        to the device state.  ``sync=True`` (optimizers without a device-side skip): returns True if all gradients are finite."""
-        ps, arr, _keep = self._grad_table(params)
-        if not ps:
-            return True
-        st = self.state(ps[0].device)
-        base = st.data_ptr()
-        L.call("mc_grads_unscale_dev", arr, len(ps), base + 4 * self._SCALE, base + 4 * self._FLAG, ops._st())
-        return float(st[self._FLAG].item()) == 0.0 if sync else None
+        to the device state.  ``sync=True`` (optimizers without a device-side skip): returns True if all gradients are finite.
+        ``clip`` = a max_norm: the same pass also sums the squares of the unscaled gradients (mc_grads_unscale_norm_dev) and
+        the call returns (that answer, the device pair [norm, clip coefficient] of ops.grad_norm_coef)."""
+        params = list(params)
+        dev = next((p.grad.device for p in params if p.grad is not None), None)
+        if dev is None:
+            return True if clip is None else (True, None)
+        st = self.state(dev)
+        scale_flag = (st.data_ptr() + 4 * self._SCALE, st.data_ptr() + 4 * self._FLAG)
+        if clip is None:
+            ps, arr, _keep = self._grad_table(params)
+            L.call("mc_grads_unscale_dev", arr, len(ps), *scale_flag, ops._st())
+        else:
+            out2 = ops.grad_norm_coef(params, clip, unscale=scale_flag, who="LossScaler")
+        ok = float(st[self._FLAG].item()) == 0.0 if sync else None
+        return ok if clip is None else (ok, out2)
 
     def update(self, opt_skipped=None):
         """GradScaler.update() on the device; ``opt_skipped``: the optimizer's own device counter of skipped steps"""
@@ -209,8 +208,14 @@ class LossScaler:
 class Trainer:
     def __init__(self, model, loss_func, optimizer, scheduler=None, device=None, bucket_mb: int = 256,
                  overlap_micro: bool = False, keep_graphs: int = 1, grad_sink: bool = True, keep_recompute: Optional[int] = None,
-                 stat_tapes: bool = True, loss_scale="auto"):
+                 stat_tapes: bool = True, loss_scale="auto", max_grad_norm: Optional[float] = None):
         self.model, self.loss_func, self.optimizer, self.scheduler = model, loss_func, optimizer, scheduler
+        # gradient-norm clipping (torch.nn.utils.clip_grad_norm_ between unscale and step): None = off; a positive number
+        # clips the rank-averaged gradients to that global L2 norm, float("inf") only reports the norm (``grad_norm``)
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be None or a positive number, got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._norm_coef = None                  # device pair [norm, clip coefficient] of the last step (max_grad_norm set)
         # loss scaling: "auto" = a dynamic LossScaler in the f16 storage build (the reference's GradScaler), none in the
         # bf16 build (fp32's exponent range); a number = that static scale; a LossScaler = yours; None = off
         if loss_scale == "auto" and os.environ.get("MC_LOSS_SCALE"):
@@ -290,19 +295,45 @@ class Trainer:
     def _optimizer_step(self):
         """optimizer update; under a loss scale: unscale the (already rank-averaged) gradients first and skip the update
         if any of them is non-finite, like GradScaler.step() [ref: trainer_ddp.py:300-303] -- without a host sync when the
-        optimizer is the HIP AdamW (the kernel reads the flag); any other optimizer: one flag read per step"""
-        if self.scaler is None:
+        optimizer is the HIP AdamW (the kernel reads the flag); any other optimizer: one flag read per step.
+        With ``max_grad_norm``: the global norm of the unscaled gradients and the clip coefficient are formed on the device
+        (by the unscale pass itself under a scaler); the HIP AdamW multiplies by the coefficient as it loads the gradients
+        (``p.grad`` stays unclipped), any other optimizer has its gradients scaled in place first."""
+        clip = self.max_grad_norm
+        if self.scaler is None and clip is None:
             self.optimizer.step()
             return
         params = list(self.model.parameters())
-        if hasattr(self.optimizer, "step_loss_scaled"):
-            self.scaler.unscale_(params)
-            opt_skipped = self.optimizer.step_loss_scaled(self.scaler)
+        hip_adamw = hasattr(self.optimizer, "step_loss_scaled")
+        if self.scaler is None:
+            nc = self._norm_coef = ops.grad_norm_coef(params, clip, who="Trainer")
+            if nc is None:                                  # (no parameter has a gradient)
+                self.optimizer.step()
+            elif hip_adamw:
+                self.optimizer.step(grad_coef=nc[1:])
+            else:
+                ops.grads_scale_(params, nc[1:])
+                self.optimizer.step()
+            return
+        nc = None
+        if hip_adamw:
+            if clip is None:
+                self.scaler.unscale_(params)
+            else:
+                nc = self.scaler.unscale_(params, clip=clip)[1]
+            opt_skipped = self.optimizer.step_loss_scaled(self.scaler, grad_coef=None if nc is None else nc[1:])
             self.scaler.update(opt_skipped)
         else:
-            if self.scaler.unscale_(params, sync=True):
+            if clip is None:
+                ok = self.scaler.unscale_(params, sync=True)
+            else:
+                ok, nc = self.scaler.unscale_(params, sync=True, clip=clip)
+            if ok:
+                if nc is not None:
+                    ops.grads_scale_(params, nc[1:])
                 self.optimizer.step()
             self.scaler.update()
+        self._norm_coef = nc
         self._steps_done = getattr(self, "_steps_done", 0) + 1
         if self._steps_done % self.scaler_check_every == 0:
             self.scaler.check()
@@ -317,6 +348,9 @@ class Trainer:
             # are not loss terms.
             out["loss_scale"] = self.scaler._state[LossScaler._SCALE].clone()
             out["skipped_steps"] = self.scaler._state[LossScaler._SKIPPED].clone()
+        if self._norm_coef is not None:
+            # the global L2 norm of the step's (unscaled, rank-averaged) gradients before clipping; non-finite on a skipped step
+            out["grad_norm"] = self._norm_coef[0].clone()
         return out
 
     def _backward(self, run):

@@ -102,6 +102,11 @@ _SIGS = {
     "mc_grads_unscale_dev": ([C.POINTER(AdamwTensor), I, P, P, P], I),
     "mc_adamw_step_ls": ([C.POINTER(AdamwTensor), I, D, D, D, D, D, LL, P, P, P], I),
     "mc_loss_scale_update": ([P, P, D, D, I, I, P], I),
+    "mc_grad_norm_partials": ([C.POINTER(AdamwTensor), I], LL),
+    "mc_grad_norm": ([C.POINTER(AdamwTensor), I, P, LL, F, P, P], I),
+    "mc_grads_unscale_norm_dev": ([C.POINTER(AdamwTensor), I, P, P, P, LL, F, P, P], I),
+    "mc_grads_scale_dev": ([C.POINTER(AdamwTensor), I, P, P], I),
+    "mc_adamw_step_clip": ([C.POINTER(AdamwTensor), I, D, D, D, D, D, LL, P, P, P, P], I),
     "mc_gemm_bf16": ([C.POINTER(GemmArgs), P], I),
     "mc_gemm_stat_rows": ([C.POINTER(GemmArgs)], I),
     "mc_gemm_tile_config": ([C.POINTER(GemmArgs)], I),

@@ -1495,6 +1495,90 @@ def dwconv_bwd_weight(x, dy, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, pro=No
     return _OP_DWCONV_WGRAD(x, dy, n, h, w, k, stride, pad_l, pad_t, oh, ow, ps, pf)
 
 
+# ------------------------------------------------------------------------------------------- gradient norm / clipping
+# Global L2 norm of the parameter gradients and clipping by it (torch.nn.utils.clip_grad_norm_), on the device with no host
+# read: per-chunk fp64 sums of squares, one finish launch, a [norm, coefficient] device pair (optim.hip).
+_NORM_WS = {}      # (device index, raw stream) -> fp64 workspace of per-chunk sums, grown on demand and reused
+
+
+def grad_table(params, who):
+    """(parameters that have a gradient, mc_adamw_tensor table with .grad / .numel filled in, the gradients)"""
+    ps = [p for p in params if p.grad is not None]
+    arr = (L.AdamwTensor * max(len(ps), 1))()
+    keep = []
+    for a, p in zip(arr, ps):
+        g = p.grad
+        if not g.is_contiguous() or g.dtype != torch.float32:
+            raise L.MammoClipHipError(f"{who}: parameter gradients must be dense contiguous fp32 tensors")
+        keep.append(g)
+        a.grad, a.numel = g.data_ptr(), g.numel()
+    return ps, arr, keep
+
+
+def _check_max_norm(max_norm):
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:                                 # (false for nan)
+        raise ValueError(f"max_norm must be a positive number (float('inf'): the norm alone), got {max_norm}")
+    return max_norm
+
+
+def grad_norm_coef(params, max_norm=float("inf"), unscale=None, who="grad_norm"):
+    """fp32 device pair [total L2 norm of the gradients, min(1, max_norm / (norm + 1e-6))], or None when no parameter has a
+    gradient.  ``unscale`` = (device pointer of the loss scale, device pointer of the non-finite flag): the gradients are
+    unscaled in place by the same pass (mc_grads_unscale_norm_dev), the norm is that of the unscaled values."""
+    max_norm = _check_max_norm(max_norm)
+    ps, arr, grads = grad_table(params, who)
+    if not ps:
+        return None
+    _chk_dev(*grads)
+    dev, st = grads[0].device, _st()
+    need = L.load().mc_grad_norm_partials(arr, len(ps))
+    ws = _NORM_WS.get((dev.index, st))
+    if ws is None or ws.numel() < need:
+        ws = _NORM_WS[(dev.index, st)] = torch.empty(max(need, 64), dtype=torch.float64, device=dev)
+    out2 = torch.empty(2, dtype=torch.float32, device=dev)
+    _note(sum(g.numel() for g in grads) * (4 if unscale is None else 8))
+    if unscale is None:
+        L.call("mc_grad_norm", arr, len(ps), ws.data_ptr(), ws.numel(), max_norm, out2.data_ptr(), st)
+    else:
+        L.call("mc_grads_unscale_norm_dev", arr, len(ps), unscale[0], unscale[1], ws.data_ptr(), ws.numel(), max_norm,
+               out2.data_ptr(), st)
+    return out2
+
+
+def _param_list(params):
+    return [params] if torch.is_tensor(params) else list(params)
+
+
+def grad_norm(params):
+    """total L2 norm of the gradients of ``params`` as a 0-dim device tensor (no synchronisation)"""
+    out2 = grad_norm_coef(_param_list(params))
+    return torch.tensor(0.0) if out2 is None else out2[0]
+
+
+def grads_scale_(params, coef):
+    """grad *= coef in place for every parameter gradient; ``coef``: a 1-element fp32 device tensor (mc_grads_scale_dev)"""
+    ps, arr, grads = grad_table(params, "grads_scale_")
+    if not ps:
+        return
+    _chk_dev(coef, *grads)
+    _note(sum(g.numel() for g in grads) * 8)
+    L.call("mc_grads_scale_dev", arr, len(ps), coef.data_ptr(), _st())
+    torch.autograd.graph.increment_version(grads)
+
+
+def clip_grad_norm_(params, max_norm):
+    """torch.nn.utils.clip_grad_norm_(params, max_norm) for fp32 gradients on the device: clips in place and returns the total
+    norm (before clipping) as a 0-dim device tensor, without synchronising.  The coefficient is torch's, in fp32 from the
+    rounded norm; non-finite gradients give a nan coefficient (torch's error_if_nonfinite=False)."""
+    params = _param_list(params)
+    out2 = grad_norm_coef(params, max_norm, who="clip_grad_norm_")
+    if out2 is None:
+        return torch.tensor(0.0)
+    grads_scale_(params, out2[1:])
+    return out2[0]
+
+
 # ------------------------------------------------------------------------------------------- gradient sink
 class GradSink:
     """Parameter gradients of the hand-written backward functions, combined by multi-tensor adds.
