@@ -273,12 +273,29 @@ typedef struct mc_dwconv_args {
      * input geometry) and the e rows the epilogue / weight gradient need are formed from it in the staging (cin <= 64). */
     const mc_bf16* xw;
     int cin;
+    /* The store-and-sum ending of the WEIGHT GRADIENT (mc_dwconv_bwd_weight, mc_dwconv_bwd_fused, mc_dwconv_bwd_data with xw +
+     * dw_out): with dw_partials != NULL no float atomic is issued -- the unit that adds its partial sums to the gradient with
+     * atomicAdd otherwise (the wave's y slot of the lane = column kernel, the persistent workgroup of the marching kernels)
+     * stores them to its own row of dw_partials: float[dw_rows][k*k][c], rows in the conv's own tap order, every element of every
+     * row written by the launch (no fill needed).  A second launch on the same stream then finishes
+     * dw[t][c] += (float) sum_r (double) dw_partials[r][t][c], r ascending (mc_ordered_sum): bit-reproducible, and still +=.
+     * dw_rows = what mc_dwconv_bwd_weight_dw_rows / _bwd_fused_dw_rows / _bwd_data_dw_rows returned for THIS argument block;
+     * 0 = not checked, and a launch whose kernel form would write another row count is refused (the stat_rows rule).
+     * NULL = the atomic ending, unchanged. */
+    float* dw_partials;
+    int dw_rows;
 } mc_dwconv_args;
 int mc_dwconv_stat_rows(const mc_dwconv_args* args);
 int mc_dwconv_bwd_data_stat_rows(const mc_dwconv_args* args);
 int mc_dwconv_fwd(const mc_dwconv_args* args, void* stream);
 int mc_dwconv_bwd_data(const mc_dwconv_args* args, void* stream);
 int mc_dwconv_bwd_weight(const mc_dwconv_args* args, void* stream);
+/* rows of args->dw_partials that the launch writes for THIS argument block under the current lane mode (pure functions of the
+ * geometry fields; pointers are only tested for NULL): mc_dwconv_bwd_weight (its form follows mc_dwconv_set_lane_mode),
+ * mc_dwconv_bwd_data with xw + dw_out (= mc_dwconv_bwd_data_stat_rows), mc_dwconv_bwd_fused (= its stat rows). */
+int mc_dwconv_bwd_weight_dw_rows(const mc_dwconv_args* args);
+int mc_dwconv_bwd_data_dw_rows(const mc_dwconv_args* args);
+int mc_dwconv_bwd_fused_dw_rows(const mc_dwconv_args* args);
 /* The E-free form of mc_dwconv_bwd_data for a STRIDE-2 3x3 conv whose input was silu(bn0(e))
  * [ref: efficientnet_custom.py:104-111 backwards: _depthwise_conv, _bn0 + swish, with e = _expand_conv(x)]: with args->xw
  * (+ cin <= 64, cin % 8 == 0) the launch does not READ e: epi_x is the block input x [n,h,w,cin] and e = x . xw^T is formed on
@@ -465,6 +482,30 @@ int mc_add_ln_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const
                   const float* mean, const float* rstd, long long rows, int h, float p,
                   unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres,
                   float* dgamma, float* dbeta, void* stream);
+/* mc_add_ln_bwd without float atomics: every workgroup stores its 2*h sums to its row of ws: float[ws_rows][2][h] with
+ * ws_rows = mc_add_ln_bwd_ws_rows(rows) (the capped grid; another count is refused), every element written, then
+ * dgamma / dbeta += the rows summed in row order (mc_ordered_sum).  dx / dres are the bits of mc_add_ln_bwd. */
+int mc_add_ln_bwd_ws_rows(long long rows);
+int mc_add_ln_bwd_ws(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const float* gamma,
+                     const float* mean, const float* rstd, long long rows, int h, float p,
+                     unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres,
+                     float* dgamma, float* dbeta, float* ws, int ws_rows, void* stream);
+/* mc_bert_embed_bwd without float atomics (store-and-sum).  ws: float[mc_bert_embed_bwd_ws_floats(b, t, h, b * t, plan)] =
+ * dx of every token row [b*t][h] | position sums per batch group [plan[0]][t][h] | gamma / beta / type-0 / type-1 sums per
+ * workgroup [plan[1]][4][h]; every element is written by the launch.  Then dword[id] += the dx rows of the tokens that name id,
+ * summed in ascending token-row order by one wave per vocabulary row (rows no token names are not touched), dpos += the groups
+ * in group order, dtype / dgamma / dbeta += the workgroups in order (mc_ordered_sum): all outputs accumulated (+=), fp64
+ * accumulators, one rounding.  sorted_ids / order: int64 [b*t], the token ids sorted ascending by a STABLE sort and the token
+ * row (index into the flattened ids) of each sorted entry.  plan (optional): int[2] = batch groups, workgroups. */
+long long mc_bert_embed_bwd_ws_floats(int b, int t, int h, long long rows, int* plan);
+int mc_bert_embed_bwd_ws(const mc_bf16* dy, const long long* ids, const long long* tt, const float* word, const float* pos,
+                         const float* type, const float* gamma, const float* mean, const float* rstd, int b, int t, int h,
+                         float p, unsigned long long seed, unsigned int stream_id, float* dword, float* dpos, float* dtype,
+                         float* dgamma, float* dbeta, const long long* sorted_ids, const long long* order, float* ws,
+                         long long ws_floats, void* stream);
+/* out[i] = (accumulate ? out[i] : 0) + (float) sum_r (double) ws[r * ld + i], 0 <= i < n <= ld, r = 0 .. rows-1 ascending:
+ * one fp64 accumulator per element and one rounding -- the finish step of every store-and-sum reduction above and below. */
+int mc_ordered_sum(const float* ws, int rows, long long ld, long long n, float* out, int accumulate, void* stream);
 /* row softmax of fp32 scores [rows, t] -> probs (bf16) and dropped probs (bf16; may alias probs when p == 0) */
 int mc_softmax_fwd(const float* scores, long long rows, int t, float p, unsigned long long seed,
                    unsigned int stream_id, mc_bf16* probs, mc_bf16* probs_drop, void* stream);
@@ -526,6 +567,14 @@ int mc_bert_embed_rows_bwd(const mc_bf16* dy, const long long* ids, const long l
                            const float* mean, const float* rstd, int b, int max_len, int t_pad, int h, float p,
                            unsigned long long seed, unsigned int stream_id, float* dword, float* dpos, float* dtype,
                            float* dgamma, float* dbeta, void* stream);
+/* mc_bert_embed_bwd_ws on packed rows: real_rows = cu_seqlens[b] token rows (the alignment rows behind them are not looked
+ * at), ws: float[mc_bert_embed_bwd_ws_floats(b, max_len, h, real_rows, plan)], sorted_ids / order over the first real_rows ids. */
+int mc_bert_embed_rows_bwd_ws(const mc_bf16* dy, const long long* ids, const long long* tt, const int* cu_seqlens,
+                              const float* word, const float* pos, const float* type, const float* gamma,
+                              const float* mean, const float* rstd, int b, int max_len, int t_pad, int h,
+                              long long real_rows, float p, unsigned long long seed, unsigned int stream_id, float* dword,
+                              float* dpos, float* dtype, float* dgamma, float* dbeta, const long long* sorted_ids,
+                              const long long* order, float* ws, long long ws_floats, void* stream);
 /* mc_add_ln_fwd / _bwd on packed rows [ref: transformers BertSelfOutput / BertOutput via text_encoder.py:47-49]; alignment
  * rows are normalised without dropout (finite in, finite out). */
 int mc_add_ln_rows_fwd(const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma, const float* beta,
@@ -534,6 +583,11 @@ int mc_add_ln_rows_fwd(const mc_bf16* x, const mc_bf16* res, const int* row_map,
 int mc_add_ln_rows_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma,
                        const float* mean, const float* rstd, long long rows, int h, float p, unsigned long long seed,
                        unsigned int stream_id, mc_bf16* dx, mc_bf16* dres, float* dgamma, float* dbeta, void* stream);
+/* ... and its store-and-sum form, see mc_add_ln_bwd_ws */
+int mc_add_ln_rows_bwd_ws(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma,
+                          const float* mean, const float* rstd, long long rows, int h, float p, unsigned long long seed,
+                          unsigned int stream_id, mc_bf16* dx, mc_bf16* dres, float* dgamma, float* dbeta, float* ws,
+                          int ws_rows, void* stream);
 /* Pooling from packed rows [ref: model/clip.py:65-75]: eos = gather of rows cu_seqlens[i+1]-1, bos = rows cu_seqlens[i]
  * (out[i] = float(src[idx[i]]); the backward scatters into a zero-filled dsrc), mean = per-sequence mean. */
 int mc_rows_gather(const mc_bf16* src, const int* idx, int n, int h, float* out, void* stream);

@@ -93,22 +93,28 @@ __global__ __launch_bounds__(256) void embed_fwd_k(const long long* __restrict__
 // wave w owns position tp = w % t and batch rows bi = w / t, w / t + nbw, ...
 // MAP: packed rows -- sequence bi owns rows cu[bi] .. cu[bi+1]-1 of dy / ids / tt / mean / rstd, t is the longest
 // sequence and tdrop the T of the padded layout (dropout element index)
-template <bool MAP>
-__global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy, const long long* __restrict__ ids,
-                                                   const int* __restrict__ cu, int tdrop,
-                                                   const long long* __restrict__ tt, const float* __restrict__ word,
-                                                   const float* __restrict__ pos, const float* __restrict__ type,
-                                                   const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                   const float* __restrict__ rstd, int b, int t, int h, int nbw, float p,
-                                                   unsigned long long seed, unsigned int sid, float* __restrict__ dword,
-                                                   float* __restrict__ dpos, float* __restrict__ dtype,
-                                                   float* __restrict__ dgamma, float* __restrict__ dbeta) {
+// DET (the store-and-sum ending, no float atomics): the wave stores each token row's dx to dxrows [rows][h] (summed per
+// vocabulary row by embed_dword_sum_k), its position sums to ws_pos [nbw][t][h], and the workgroup its gamma / beta / type-0 /
+// type-1 sums (4 waves combined through LDS in wave order) to ws_gb [gridDim.x][4][h]; mc_ordered_sum finishes the last two
+template <bool MAP, bool DET>
+__device__ __forceinline__ void embed_bwd_body(const bf16_t* __restrict__ dy, const long long* __restrict__ ids,
+                                               const int* __restrict__ cu, int tdrop,
+                                               const long long* __restrict__ tt, const float* __restrict__ word,
+                                               const float* __restrict__ pos, const float* __restrict__ type,
+                                               const float* __restrict__ gamma, const float* __restrict__ mean,
+                                               const float* __restrict__ rstd, int b, int t, int h, int nbw, float p,
+                                               unsigned long long seed, unsigned int sid, float* __restrict__ dword,
+                                               float* __restrict__ dpos, float* __restrict__ dtype,
+                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                               float* __restrict__ dxrows, float* __restrict__ ws_pos,
+                                               float* __restrict__ ws_gb) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nvec = h / 8;
     const long long gw = (long long)blockIdx.x * 4 + wave;
-    if (gw >= (long long)t * nbw) return;
+    const bool live = gw < (long long)t * nbw;
+    if (!DET && !live) return;                 // (DET: the waves past the last position take part in the LDS combine with zeros)
     const int tp = (int)(gw % t);
-    const int bg = (int)(gw / t);
+    const int bg = live ? (int)(gw / t) : b;
     float aps[MAXV][8], agm[MAXV][8], abt[MAXV][8], at0[MAXV][8], at1[MAXV][8], g[MAXV][8];
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
@@ -165,10 +171,35 @@ __global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy
                     float dx = rs * (dg[i][q] - s1 - xh[i][q] * s2);
                     aps[i][q] += dx;
                     if (ty == 0) at0[i][q] += dx; else at1[i][q] += dx;
-                    atomicAdd(dword + id * h + v * 8 + q, dx);
+                    if constexpr (DET) dxrows[row * h + v * 8 + q] = dx;
+                    else atomicAdd(dword + id * h + v * 8 + q, dx);
                 }
             }
         }
+    }
+    if constexpr (DET) {
+        __shared__ float red[4][MAXV * 64 * 16];
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {                  // 0: gamma | beta, 1: type 0 | type 1
+            if (pass) __syncthreads();
+#pragma unroll
+            for (int i = 0; i < MAXV; ++i)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    red[wave][((i * 64 + lane) * 16) + q] = pass ? at0[i][q] : agm[i][q];
+                    red[wave][((i * 64 + lane) * 16) + 8 + q] = pass ? at1[i][q] : abt[i][q];
+                    if (pass == 0 && live && lane + i * 64 < nvec) ws_pos[((long long)bg * t + tp) * h + (lane + i * 64) * 8 + q] = aps[i][q];
+                }
+            __syncthreads();
+            for (int e = threadIdx.x; e < nvec * 16; e += 256) {
+                int v = e / 16, q = e % 16;
+                int i = v / 64, ln = v % 64;
+                float sv = 0.f;
+                for (int w = 0; w < 4; ++w) sv += red[w][((i * 64 + ln) * 16) + q];
+                ws_gb[((long long)blockIdx.x * 4 + pass * 2 + q / 8) * h + v * 8 + q % 8] = sv;
+            }
+        }
+        return;
     }
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
@@ -183,6 +214,69 @@ __global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy
                 if (at1[i][q] != 0.f) atomicAdd(dtype + h + v * 8 + q, at1[i][q]);
             }
         }
+    }
+}
+template <bool MAP>
+__global__ __launch_bounds__(256) void embed_bwd_k(const bf16_t* __restrict__ dy, const long long* __restrict__ ids,
+                                                   const int* __restrict__ cu, int tdrop,
+                                                   const long long* __restrict__ tt, const float* __restrict__ word,
+                                                   const float* __restrict__ pos, const float* __restrict__ type,
+                                                   const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                   const float* __restrict__ rstd, int b, int t, int h, int nbw, float p,
+                                                   unsigned long long seed, unsigned int sid, float* __restrict__ dword,
+                                                   float* __restrict__ dpos, float* __restrict__ dtype,
+                                                   float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    embed_bwd_body<MAP, false>(dy, ids, cu, tdrop, tt, word, pos, type, gamma, mean, rstd, b, t, h, nbw, p, seed, sid, dword, dpos,
+                               dtype, dgamma, dbeta, nullptr, nullptr, nullptr);
+}
+template <bool MAP>
+__global__ __launch_bounds__(256) void embed_bwd_ws_k(const bf16_t* __restrict__ dy, const long long* __restrict__ ids,
+                                                      const int* __restrict__ cu, int tdrop,
+                                                      const long long* __restrict__ tt, const float* __restrict__ word,
+                                                      const float* __restrict__ pos, const float* __restrict__ type,
+                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                      const float* __restrict__ rstd, int b, int t, int h, int nbw, float p,
+                                                      unsigned long long seed, unsigned int sid, float* __restrict__ dxrows,
+                                                      float* __restrict__ ws_pos, float* __restrict__ ws_gb) {
+    embed_bwd_body<MAP, true>(dy, ids, cu, tdrop, tt, word, pos, type, gamma, mean, rstd, b, t, h, nbw, p, seed, sid, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, dxrows, ws_pos, ws_gb);
+}
+// dword[id] += (float) sum (double) dxrows[row] over the token rows that name id, in ascending row order.  sorted_ids / order:
+// the n token ids sorted ascending (stable) and the token row of each; the wave at the FIRST sorted position of an id owns
+// that vocabulary row, the others leave -- ids that no token names are not touched
+__global__ __launch_bounds__(256) void embed_dword_sum_k(const long long* __restrict__ sorted_ids,
+                                                         const long long* __restrict__ order, long long n,
+                                                         const float* __restrict__ dxrows, int h, float* __restrict__ dword) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nvec = h / 8;
+    const long long j0 = (long long)blockIdx.x * 4 + wave;
+    if (j0 >= n) return;
+    const long long id = sorted_ids[j0];
+    if (j0 > 0 && sorted_ids[j0 - 1] == id) return;
+    double acc[MAXV][8];
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[i][q] = 0.0;
+    for (long long j = j0; j < n && sorted_ids[j] == id; ++j) {
+        const float* src = dxrows + order[j] * h;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            int v = lane + i * 64;
+            if (v < nvec) {
+                float d[8];
+                load8f(src + v * 8, d);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc[i][q] += (double)d[q];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        int v = lane + i * 64;
+        if (v < nvec)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) dword[id * h + v * 8 + q] += (float)acc[i][q];
     }
 }
 
@@ -242,7 +336,8 @@ __global__ __launch_bounds__(256) void add_ln_bwd_k(const bf16_t* __restrict__ d
                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
                                                     long long rows, int h, float p, unsigned long long seed,
                                                     unsigned int sid, bf16_t* __restrict__ dx, bf16_t* __restrict__ dres,
-                                                    float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                    float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                    float* __restrict__ ws) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nvec = h / 8;
     float agm[MAXV][8], abt[MAXV][8], g[MAXV][8];
@@ -300,6 +395,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_k(const bf16_t* __restrict__ d
         }
     }
     // block reduce of dgamma / dbeta over the 4 waves, then one atomic per element per workgroup
+    // (ws != NULL: a plain store into the workgroup's row of ws [gridDim.x][2][h] instead; mc_ordered_sum finishes)
     __shared__ float red[4][MAXV * 64 * 16];
 #pragma unroll
     for (int i = 0; i < MAXV; ++i)
@@ -314,7 +410,8 @@ __global__ __launch_bounds__(256) void add_ln_bwd_k(const bf16_t* __restrict__ d
         int i = v / 64, ln = v % 64;
         float s = 0.f;
         for (int w = 0; w < 4; ++w) s += red[w][((i * 64 + ln) * 16) + q];
-        if (q < 8) atomicAdd(dgamma + v * 8 + q, s);
+        if (ws) ws[((long long)blockIdx.x * 2 + q / 8) * h + v * 8 + q % 8] = s;
+        else if (q < 8) atomicAdd(dgamma + v * 8 + q, s);
         else atomicAdd(dbeta + v * 8 + (q - 8), s);
     }
 }
@@ -538,14 +635,43 @@ int row_blocks(long long rows) {
     return (int)b;
 }
 
+// work split of the embedding backward: batch groups per position, workgroups
+int embed_bwd_nbw(int b, int t) {
+    int nbw = 2048 / t;
+    if (nbw < 1) nbw = 1;
+    if (nbw > b) nbw = b;
+    return nbw;
+}
+// the store-and-sum form (no float atomics): ws = dxrows [rows][h] | ws_pos [nbw][t][h] | ws_gb [workgroups][4][h]; `rows` token
+// rows (padded: b * t), sorted_ids / order: their ids sorted ascending (stable) and the row of each
+int launch_embed_bwd_ws(const mc_bf16* dy, const long long* ids, const long long* tt, const int* cu_seqlens, const float* word,
+                        const float* pos, const float* type, const float* gamma, const float* mean, const float* rstd, int b, int t,
+                        int t_pad, int h, long long rows, float p, unsigned long long seed, unsigned int stream_id, float* dword,
+                        float* dpos, float* dtype, float* dgamma, float* dbeta, const long long* sorted_ids, const long long* order,
+                        float* ws, long long ws_floats, void* stream) {
+    int plan[2];
+    MC_CHECK(ws_floats == mc_bert_embed_bwd_ws_floats(b, t, h, rows, plan), "embed_bwd_ws: ws was sized for another shape");
+    const int nbw = plan[0], groups = plan[1];
+    float* dxrows = ws;
+    float* ws_pos = dxrows + rows * h;
+    float* ws_gb = ws_pos + (long long)nbw * t * h;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(cu_seqlens ? embed_bwd_ws_k<true> : embed_bwd_ws_k<false>, dim3(groups), dim3(256), 0, st, dy, ids, cu_seqlens,
+                       t_pad, tt, word, pos, type, gamma, mean, rstd, b, t, h, nbw, p, seed, stream_id, dxrows, ws_pos, ws_gb);
+    MC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(embed_dword_sum_k, dim3(mc_div_up(rows, 4)), dim3(256), 0, st, sorted_ids, order, rows, dxrows, h, dword);
+    MC_LAUNCH_CHECK();
+    if (int e = mc_ordered_sum(ws_pos, nbw, (long long)t * h, (long long)t * h, dpos, 1, stream)) return e;
+    if (int e = mc_ordered_sum(ws_gb, groups, 4ll * h, h, dgamma, 1, stream)) return e;
+    if (int e = mc_ordered_sum(ws_gb + h, groups, 4ll * h, h, dbeta, 1, stream)) return e;
+    return mc_ordered_sum(ws_gb + 2 * h, groups, 4ll * h, 2ll * h, dtype, 1, stream);
+}
 // embedding backward over t positions of b sequences; cu_seqlens set: packed rows, dropout indices of the [b, t_pad] layout
 int launch_embed_bwd(const mc_bf16* dy, const long long* ids, const long long* tt, const int* cu_seqlens, const float* word,
                      const float* pos, const float* type, const float* gamma, const float* mean, const float* rstd, int b, int t,
                      int t_pad, int h, float p, unsigned long long seed, unsigned int stream_id, float* dword, float* dpos,
                      float* dtype, float* dgamma, float* dbeta, void* stream) {
-    int nbw = 2048 / t;
-    if (nbw < 1) nbw = 1;
-    if (nbw > b) nbw = b;
+    const int nbw = embed_bwd_nbw(b, t);
     long long waves = (long long)t * nbw;
     hipLaunchKernelGGL(cu_seqlens ? embed_bwd_k<true> : embed_bwd_k<false>, dim3(mc_div_up(waves, 4)), dim3(256), 0, (hipStream_t)stream,
                        dy, ids, cu_seqlens, t_pad, tt, word, pos, type, gamma, mean, rstd, b, t, h, nbw, p, seed, stream_id, dword, dpos,
@@ -566,14 +692,16 @@ int launch_add_ln_fwd(const char* shape_msg, const mc_bf16* x, const mc_bf16* re
 int launch_add_ln_bwd(const char* shape_msg, const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map,
                       const float* gamma, const float* mean, const float* rstd, long long rows, int h, float p,
                       unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres, float* dgamma,
-                      float* dbeta, void* stream) {
+                      float* dbeta, float* ws, int ws_rows, void* stream) {
     MC_CHECK(rows > 0 && h > 0 && h % 8 == 0 && h <= 1024, shape_msg);
-    long long blocks = (rows + 3) / 4;
-    if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(row_map ? add_ln_bwd_k<true> : add_ln_bwd_k<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dy,
-                       x, res, row_map, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres, dgamma, dbeta);
+    const int blocks = mc_add_ln_bwd_ws_rows(rows);
+    MC_CHECK(!ws || ws_rows == blocks, "add_ln_bwd_ws: ws was sized for another row count (ws_rows != mc_add_ln_bwd_ws_rows)");
+    hipLaunchKernelGGL(row_map ? add_ln_bwd_k<true> : add_ln_bwd_k<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy,
+                       x, res, row_map, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres, dgamma, dbeta, ws);
     MC_LAUNCH_CHECK();
-    return MC_OK;
+    if (!ws) return MC_OK;
+    if (int e = mc_ordered_sum(ws, blocks, 2ll * h, h, dgamma, 1, stream)) return e;
+    return mc_ordered_sum(ws + h, blocks, 2ll * h, h, dbeta, 1, stream);
 }
 
 }  // namespace
@@ -612,7 +740,39 @@ extern "C" int mc_add_ln_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_bf16*
                              float* dbeta, void* stream) {
     MC_CHECK(dy && x && res && gamma && mean && rstd && dx && dres && dgamma && dbeta, "add_ln_bwd: null arg");
     return launch_add_ln_bwd("add_ln_bwd: bad shape", dy, x, res, nullptr, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres, dgamma,
-                             dbeta, stream);
+                             dbeta, nullptr, 0, stream);
+}
+extern "C" int mc_add_ln_bwd_ws_rows(long long rows) {
+    long long blocks = (rows + 3) / 4;
+    if (blocks > 512) blocks = 512;
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
+}
+extern "C" int mc_add_ln_bwd_ws(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const float* gamma,
+                                const float* mean, const float* rstd, long long rows, int h, float p,
+                                unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres, float* dgamma,
+                                float* dbeta, float* ws, int ws_rows, void* stream) {
+    MC_CHECK(dy && x && res && gamma && mean && rstd && dx && dres && dgamma && dbeta && ws, "add_ln_bwd_ws: null arg");
+    return launch_add_ln_bwd("add_ln_bwd_ws: bad shape", dy, x, res, nullptr, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres,
+                             dgamma, dbeta, ws, ws_rows, stream);
+}
+extern "C" long long mc_bert_embed_bwd_ws_floats(int b, int t, int h, long long rows, int* plan) {
+    if (b <= 0 || t <= 0 || h <= 0 || rows <= 0) return 0;
+    const int nbw = embed_bwd_nbw(b, t), groups = mc_div_up((long long)t * nbw, 4);
+    if (plan) { plan[0] = nbw; plan[1] = groups; }
+    return (rows + (long long)nbw * t + 4ll * groups) * h;
+}
+extern "C" int mc_bert_embed_bwd_ws(const mc_bf16* dy, const long long* ids, const long long* tt, const float* word,
+                                    const float* pos, const float* type, const float* gamma, const float* mean,
+                                    const float* rstd, int b, int t, int h, float p, unsigned long long seed,
+                                    unsigned int stream_id, float* dword, float* dpos, float* dtype, float* dgamma,
+                                    float* dbeta, const long long* sorted_ids, const long long* order, float* ws,
+                                    long long ws_floats, void* stream) {
+    MC_CHECK(dy && ids && word && pos && type && gamma && mean && rstd && dword && dpos && dtype && dgamma && dbeta && sorted_ids &&
+             order && ws, "embed_bwd_ws: null arg");
+    MC_CHECK(b > 0 && t > 0 && h > 0 && h % 8 == 0 && h <= 1024, "embed_bwd_ws: bad shape");
+    return launch_embed_bwd_ws(dy, ids, tt, nullptr, word, pos, type, gamma, mean, rstd, b, t, t, h, (long long)b * t, p, seed, stream_id,
+                               dword, dpos, dtype, dgamma, dbeta, sorted_ids, order, ws, ws_floats, stream);
 }
 extern "C" int mc_softmax_fwd(const float* scores, long long rows, int t, float p, unsigned long long seed,
                               unsigned int stream_id, mc_bf16* probs, mc_bf16* probs_drop, void* stream) {
@@ -764,6 +924,20 @@ extern "C" int mc_bert_embed_rows_bwd(const mc_bf16* dy, const long long* ids, c
     return launch_embed_bwd(dy, ids, tt, cu_seqlens, word, pos, type, gamma, mean, rstd, b, max_len, t_pad, h, p, seed, stream_id, dword,
                             dpos, dtype, dgamma, dbeta, stream);
 }
+extern "C" int mc_bert_embed_rows_bwd_ws(const mc_bf16* dy, const long long* ids, const long long* tt, const int* cu_seqlens,
+                                         const float* word, const float* pos, const float* type, const float* gamma,
+                                         const float* mean, const float* rstd, int b, int max_len, int t_pad, int h,
+                                         long long real_rows, float p, unsigned long long seed, unsigned int stream_id,
+                                         float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta,
+                                         const long long* sorted_ids, const long long* order, float* ws, long long ws_floats,
+                                         void* stream) {
+    MC_CHECK(dy && ids && cu_seqlens && word && pos && type && gamma && mean && rstd && dword && dpos && dtype && dgamma && dbeta &&
+             sorted_ids && order && ws, "embed_rows_bwd_ws: null arg");
+    MC_CHECK(b > 0 && max_len > 0 && t_pad >= max_len && h > 0 && h % 8 == 0 && h <= 1024 && real_rows >= b &&
+             real_rows <= (long long)b * max_len, "embed_rows_bwd_ws: bad shape");
+    return launch_embed_bwd_ws(dy, ids, tt, cu_seqlens, word, pos, type, gamma, mean, rstd, b, max_len, t_pad, h, real_rows, p, seed,
+                               stream_id, dword, dpos, dtype, dgamma, dbeta, sorted_ids, order, ws, ws_floats, stream);
+}
 extern "C" int mc_add_ln_rows_fwd(const mc_bf16* x, const mc_bf16* res, const int* row_map, const float* gamma,
                                   const float* beta, float eps, long long rows, int h, float p, unsigned long long seed,
                                   unsigned int stream_id, mc_bf16* y, float* mean, float* rstd, void* stream) {
@@ -777,7 +951,15 @@ extern "C" int mc_add_ln_rows_bwd(const mc_bf16* dy, const mc_bf16* x, const mc_
                                   float* dgamma, float* dbeta, void* stream) {
     MC_CHECK(dy && x && res && row_map && gamma && mean && rstd && dx && dres && dgamma && dbeta, "add_ln_rows_bwd: null arg");
     return launch_add_ln_bwd("add_ln_rows_bwd: bad shape", dy, x, res, row_map, gamma, mean, rstd, rows, h, p, seed, stream_id, dx, dres,
-                             dgamma, dbeta, stream);
+                             dgamma, dbeta, nullptr, 0, stream);
+}
+extern "C" int mc_add_ln_rows_bwd_ws(const mc_bf16* dy, const mc_bf16* x, const mc_bf16* res, const int* row_map,
+                                     const float* gamma, const float* mean, const float* rstd, long long rows, int h, float p,
+                                     unsigned long long seed, unsigned int stream_id, mc_bf16* dx, mc_bf16* dres,
+                                     float* dgamma, float* dbeta, float* ws, int ws_rows, void* stream) {
+    MC_CHECK(dy && x && res && row_map && gamma && mean && rstd && dx && dres && dgamma && dbeta && ws, "add_ln_rows_bwd_ws: null arg");
+    return launch_add_ln_bwd("add_ln_rows_bwd_ws: bad shape", dy, x, res, row_map, gamma, mean, rstd, rows, h, p, seed, stream_id, dx,
+                             dres, dgamma, dbeta, ws, ws_rows, stream);
 }
 extern "C" int mc_rows_gather(const mc_bf16* src, const int* idx, int n, int h, float* out, void* stream) {
     MC_CHECK(src && idx && out && n > 0 && h > 0, "rows_gather: bad args");

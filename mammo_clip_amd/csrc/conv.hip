@@ -469,9 +469,13 @@ __global__ __launch_bounds__(256, (K == 3 && S == 1 && !EPI ? 3 : 2)) void dwcon
 //   dw[kh,kw,c] += dy[o, x, c] * x'[o*S + kh, x*S + kw, c]        (x' = BN+SiLU prologue applied while staging)
 // dy is staged through LDS beside x (position-major so a wave's reads are contiguous).  Accumulators run across all
 // items of the persistent workgroup; one LDS reduction + one atomic per (tap, channel) per workgroup at the end.
-template <int K, int S, int CPL, int LP, int NCOL>
+// SW = the stride, + 4 for the instantiations with the store-and-sum ending (p.dw_partials, no float atomics): a separate
+// instantiation, so the atomic ending keeps its code and its registers
+template <int K, int SW, int CPL, int LP, int NCOL>
 __global__ __launch_bounds__(256, 2) void dwconv_march_bww_kernel(const mc_dwconv_args p, int strips, int segs, int seg_rows,
                                                                   int ctiles, int gy) {
+    constexpr int S = SW & 3;
+    constexpr bool DWS = SW >= 4;
     using C = MarchCfg<K, S, CPL, LP, NCOL>;
     typedef typename std::conditional<CPL == 4, uint2, uint32_t>::type ldsv_t;
     constexpr int ORB = C::A * C::NR;                      // dy rows per staged block
@@ -681,7 +685,9 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bww_kernel(const mc_dwcon
             float s = 0.f;
             for (int wv = 0; wv < 4; ++wv)
                 for (int q = 0; q < C::PXW; ++q) s += red[(wv * 64 + q * LP + tid / CPL) * CPL + tid % CPL];
-            atomicAdd(reinterpret_cast<float*>(p.out) + (long long)t * p.c + c0 + tid, s);
+            // (DWS: a plain store into the workgroup's row y of dw_partials [gy][k*k][c]; mc_ordered_sum adds the rows)
+            if constexpr (DWS) p.dw_partials[((long long)y * (K * K) + t) * p.c + c0 + tid] = s;
+            else atomicAdd(reinterpret_cast<float*>(p.out) + (long long)t * p.c + c0 + tid, s);
         }
     }
 }
@@ -736,9 +742,13 @@ template <int K_, int CPL_, int LP_, int NJ_, bool EPI_ = false> struct MarchBwd
 // every lane reads exactly what the e-reading form prefetched.  With p.dw_out the launch is also the conv's WEIGHT gradient:
 // the scatter already meets every (dy value, tap, completed pixel) triple, so a0 = z * sigmoid(z) (the sigmoid silu' needs
 // anyway; rounded to 16 bits like the staged a0 of dwconv_march_bww_kernel) times the dy values of this and the previous row accumulates into K*K per-lane sums, reduced once per workgroup.
-template <int K, int CPL, int LP, int NJ, bool EPI = false, int KS = 0>
+// KSW = KS, + 4 for the instantiations whose weight gradient takes the store-and-sum ending (p.dw_partials), see
+// dwconv_march_bww_kernel
+template <int K, int CPL, int LP, int NJ, bool EPI = false, int KSW = 0>
 __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dwconv_args p, int strips, int segs, int seg_rows,
                                                                      int ctiles, int gy) {
+    constexpr int KS = KSW & 3;
+    constexpr bool DWS = KSW >= 4;
     using C = MarchBwdCfg<K, CPL, LP, NJ, EPI>;
     typedef typename std::conditional<CPL == 4, uint2, uint32_t>::type ldsv_t;
     constexpr bool XW = KS > 0;
@@ -1124,7 +1134,8 @@ __global__ __launch_bounds__(256, 2) void dwconv_march_bwd_s2_kernel(const mc_dw
                         float sv = 0.f;
                         for (int wv = 0; wv < 4; ++wv)
                             for (int q = 0; q < C::PXW; ++q) sv += red[(wv * 64 + q * LP + tid / CPL) * CPL + tid % CPL];
-                        atomicAdd(p.dw_out + (long long)t * p.c + c0 + tid, sv);
+                        if constexpr (DWS) p.dw_partials[((long long)y * (K * K) + t) * p.c + c0 + tid] = sv;
+                        else atomicAdd(p.dw_out + (long long)t * p.c + c0 + tid, sv);
                     }
                 }
             }
@@ -1225,17 +1236,29 @@ template <int K, int S, typename C> int launch_march(const mc_dwconv_args& p, hi
 template <int K, int S> int launch_march_cp(const mc_dwconv_args& p, hipStream_t st) {
     return march_dispatch<K, S>(p, [&](auto cfg) { return launch_march<K, S, decltype(cfg)>(p, st); }, true);
 }
-template <int K, int S, typename C> int launch_march_bww(const mc_dwconv_args& p, hipStream_t st) {
+template <typename C> MarchPlan march_bww_plan(const mc_dwconv_args& p) {
     MarchPlan m = march_plan<C>(p);
     // 2 workgroups per CU here (the whole-pixel form fits three: 156 VGPRs)
     m.gy = march_gy((long long)p.n * m.strips * m.segs, m.ctiles, C::TCH == 240 ? 3 : 2);
-    hipLaunchKernelGGL((dwconv_march_bww_kernel<K, S, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL>), dim3((m.gy + 7) / 8 * 8 * m.ctiles),
-                       dim3(256), 0, st, p, m.strips, m.segs, m.seg_rows, m.ctiles, m.gy);
+    return m;
+}
+template <int K, int S, typename C> int launch_march_bww(const mc_dwconv_args& p, hipStream_t st) {
+    const MarchPlan m = march_bww_plan<C>(p);
+    const dim3 grid((m.gy + 7) / 8 * 8 * m.ctiles);
+    if (p.dw_partials)
+        hipLaunchKernelGGL((dwconv_march_bww_kernel<K, S + 4, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL>), grid, dim3(256), 0, st, p, m.strips,
+                           m.segs, m.seg_rows, m.ctiles, m.gy);
+    else
+        hipLaunchKernelGGL((dwconv_march_bww_kernel<K, S, C::H2 * 2, C::TCH / (C::H2 * 2), C::NCOL>), grid, dim3(256), 0, st, p, m.strips,
+                           m.segs, m.seg_rows, m.ctiles, m.gy);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
 template <int K, int S> int launch_march_bww_cp(const mc_dwconv_args& p, hipStream_t st) {
     return march_dispatch<K, S>(p, [&](auto cfg) { return launch_march_bww<K, S, decltype(cfg)>(p, st); }, true);
+}
+template <int K, int S> int march_bww_rows(const mc_dwconv_args& p) {
+    return march_dispatch<K, S>(p, [&](auto cfg) { return march_bww_plan<decltype(cfg)>(p).gy; }, true);
 }
 template <int K, int S> int march_rows(const mc_dwconv_args& p) {
     return march_dispatch<K, S>(p, [&](auto cfg) { return march_plan<decltype(cfg)>(p).gy; }, true);
@@ -1264,6 +1287,7 @@ extern "C" int mc_dwconv_lane_supported(const mc_dwconv_args* a);
 extern "C" int mc_dwconv_lane_stat_rows(const mc_dwconv_args* a);
 extern "C" int mc_dwconv_fwd_lane(const mc_dwconv_args* a, void* stream);
 extern "C" int mc_dwconv_bwd_weight_lane(const mc_dwconv_args* a, void* stream);
+extern "C" int mc_dwconv_bwd_weight_lane_dw_rows(const mc_dwconv_args* a);
 std::atomic<int> g_lane_mode{-2};     // -2: not read yet; -1 policy; 0 never; 1 wherever supported
 int lane_mode() {
     int m = g_lane_mode.load(std::memory_order_relaxed);
@@ -1378,14 +1402,21 @@ extern "C" int mc_dwconv_bwd_data(const mc_dwconv_args* a, void* stream) {
     MC_CHECK(!p.dw_out || p.xw, "dwconv_bwd_data: the fused weight gradient (dw_out) is provided for the e-forming form (xw)");
     MC_CHECK(!(p.epi_x && p.stat_rows > 0) || p.stat_rows == mc_dwconv_bwd_data_stat_rows(a),
              "dwconv_bwd_data: stat_partials was sized for another configuration");
+    MC_CHECK(!p.dw_partials || p.dw_out, "dwconv_bwd_data: dw_partials belongs to the fused weight gradient (dw_out)");
+    const int dw_rows = p.dw_partials ? mc_dwconv_bwd_data_dw_rows(a) : 0;
+    MC_CHECK(!(p.dw_partials && p.dw_rows > 0) || p.dw_rows == dw_rows, "dwconv_bwd_data: dw_partials was sized for another configuration");
     hipStream_t st = (hipStream_t)stream;
     if (p.xw) {                                                        // (3x3 stride 2: mc_dwconv_bwd_data_xw_supported)
         MC_CHECK(mc_aligned16(p.epi_x) && mc_aligned16(p.xw), "dwconv_bwd_data (e from the block input): x / xw must be 16-byte aligned");
-        return march_bwd_s2_dispatch<true>(p, [&](auto cfg) {
+        const int e = march_bwd_s2_dispatch<true>(p, [&](auto cfg) {
             using C = decltype(cfg);
-            if constexpr (C::K == 3) return p.cin <= 32 ? launch_march_bwd_s2<C, 1>(p, st) : launch_march_bwd_s2<C, 2>(p, st);
-            else return (int)MC_ERR_ARG;
+            if constexpr (C::K == 3) {
+                if (p.dw_partials) return p.cin <= 32 ? launch_march_bwd_s2<C, 1 + 4>(p, st) : launch_march_bwd_s2<C, 2 + 4>(p, st);
+                return p.cin <= 32 ? launch_march_bwd_s2<C, 1>(p, st) : launch_march_bwd_s2<C, 2>(p, st);
+            } else return (int)MC_ERR_ARG;
         });
+        if (e || !p.dw_partials) return e;
+        return mc_ordered_sum(p.dw_partials, dw_rows, (long long)p.k * p.k * p.c, (long long)p.k * p.k * p.c, p.dw_out, 1, stream);
     }
     if (p.stride == 2) {                                               // marching form, with or without the epilogue
         if (p.epi_x) return march_bwd_s2_dispatch<true>(p, [&](auto cfg) { return launch_march_bwd_s2<decltype(cfg)>(p, st); });
@@ -1400,14 +1431,31 @@ extern "C" int mc_dwconv_bwd_data(const mc_dwconv_args* a, void* stream) {
     return MC_OK;
 }
 
+// rows of dw_partials [rows][k*k][c] (the store-and-sum ending of the weight gradient) that the launch writes for THIS argument
+// block under the current lane mode: the y slots of the lane = column kernel, the persistent workgroups per channel tile of the
+// marching kernels
+extern "C" int mc_dwconv_bwd_weight_dw_rows(const mc_dwconv_args* a) {
+    if (use_lane_bww(*a)) return mc_dwconv_bwd_weight_lane_dw_rows(a);
+    if (a->k == 3) return a->stride == 1 ? march_bww_rows<3, 1>(*a) : march_bww_rows<3, 2>(*a);
+    return a->stride == 1 ? march_bww_rows<5, 1>(*a) : march_bww_rows<5, 2>(*a);
+}
+extern "C" int mc_dwconv_bwd_data_dw_rows(const mc_dwconv_args* a) { return mc_dwconv_bwd_data_stat_rows(a); }
+
 extern "C" int mc_dwconv_bwd_weight(const mc_dwconv_args* a, void* stream) {
     const mc_dwconv_args& p = *a;
     if (int e = check_common(p)) return e;
     MC_CHECK(p.x && p.dy, "dwconv_bwd_weight: null x / dy");
+    const int dw_rows = p.dw_partials ? mc_dwconv_bwd_weight_dw_rows(a) : 0;
+    MC_CHECK(!(p.dw_partials && p.dw_rows > 0) || p.dw_rows == dw_rows,
+             "dwconv_bwd_weight: dw_partials was sized for another kernel form (dw_rows != mc_dwconv_bwd_weight_dw_rows now)");
     hipStream_t st = (hipStream_t)stream;
     if (use_lane_bww(p)) return mc_dwconv_bwd_weight_lane(a, stream);
-    if (p.k == 3 && p.stride == 1) return launch_march_bww_cp<3, 1>(p, st);
-    if (p.k == 3 && p.stride == 2) return launch_march_bww_cp<3, 2>(p, st);
-    if (p.k == 5 && p.stride == 1) return launch_march_bww_cp<5, 1>(p, st);
-    return launch_march_bww_cp<5, 2>(p, st);
+    int e;
+    if (p.k == 3 && p.stride == 1) e = launch_march_bww_cp<3, 1>(p, st);
+    else if (p.k == 3 && p.stride == 2) e = launch_march_bww_cp<3, 2>(p, st);
+    else if (p.k == 5 && p.stride == 1) e = launch_march_bww_cp<5, 1>(p, st);
+    else e = launch_march_bww_cp<5, 2>(p, st);
+    if (e || !p.dw_partials) return e;
+    return mc_ordered_sum(p.dw_partials, dw_rows, (long long)p.k * p.k * p.c, (long long)p.k * p.k * p.c, reinterpret_cast<float*>(p.out), 1,
+                          stream);
 }

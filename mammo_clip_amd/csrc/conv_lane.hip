@@ -109,7 +109,9 @@ constexpr int NDESC = 128;
 // fragments), which leaves every lane with 2 x 4 consecutive expanded channels of ONE pixel: BatchNorm0 + swish on the fp32
 // accumulators, zero for the static padding, 16-bit pairs into the [row][position][17 dwords] tile -- the layout the stencil
 // reads, so everything behind the staging (stencil, output tile, BatchNorm1 statistics) is MODE 0 unchanged.
-template <int K, int S, int NCOL, int MODE, int G, int KC = 0>
+// MODE_ = MODE, + 8 for the instantiations of MODE 2 / 3 / 5 whose weight gradient takes the store-and-sum ending (p.dw_partials,
+// no float atomics): separate instantiations, so the atomic ending keeps its code and its registers
+template <int K, int S, int NCOL, int MODE_, int G, int KC = 0>
 __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwconv_args p, int strips, int nunits, int cpairs,
                                                                   int ctiles, int ymax, int xmap) {
     using C = Cfg<K, S, NCOL, G>;
@@ -118,6 +120,9 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
     // [n, oh, ow, cin], xw = the expand weight) by the MFMA staging of MODE 4 instead of being read: with MODE 4 in the forward
     // the expanded tensor of a stride-1 3x3 block never exists in HBM, forward or backward.  The tile holds RAW e (16-bit, rounded
     // once from the fp32 accumulators, like the tensor the expand GEMM stores): everything behind the staging is MODE 3.
+    constexpr int MODE = MODE_ & 7;
+    constexpr bool DWS = MODE_ >= 8;
+    static_assert(!DWS || MODE == 2 || MODE == 3 || MODE == 5, "the store-and-sum ending belongs to the weight-gradient modes");
     constexpr bool XE = MODE == 5;
     constexpr bool FUSED = MODE == 3 || XE;
     constexpr bool XF = MODE == 4;
@@ -801,7 +806,21 @@ done:
         for (int t = 0; t < K * K; ++t) {
             const float a = wave_sum(dwa[t].x), b = wave_sum(dwa[t].y);
             const int tt = FUSED ? K * K - 1 - t : t;
-            if (x == 0 && ch_ok) { atomicAdd(dw + (long long)tt * p.c + cl, a); atomicAdd(dw + (long long)tt * p.c + cl + 1, b); }
+            if constexpr (DWS) {
+                // the store-and-sum ending (no float atomics): the wave's sums go to row yslot of dw_partials [ymax][k*k][c]
+                // like the statistics below; mc_ordered_sum adds the rows to dw in row order after the launch
+                if (x == 0 && ch_ok) {
+                    float* r = p.dw_partials + ((long long)yslot * (K * K) + tt) * p.c + cl;
+                    r[0] = a; r[1] = b;
+                    if (yslot == 0)
+                        for (int yy = ycp; yy < ymax; ++yy) {             // tile pairs with one y slot fewer: zero rows
+                            float* z = p.dw_partials + ((long long)yy * (K * K) + tt) * p.c + cl;
+                            z[0] = 0.f; z[1] = 0.f;
+                        }
+                }
+            } else {
+                if (x == 0 && ch_ok) { atomicAdd(dw + (long long)tt * p.c + cl, a); atomicAdd(dw + (long long)tt * p.c + cl + 1, b); }
+            }
         }
         if constexpr (BWW) return;
     }
@@ -847,9 +866,9 @@ template <typename C> Plan plan(const mc_dwconv_args& p) {
     return m;
 }
 
-template <typename C, int MODE, int KC = 0> int launch(const mc_dwconv_args& p, hipStream_t st) {
+template <typename C, int MODE, int KC = 0, bool DWS = false> int launch(const mc_dwconv_args& p, hipStream_t st) {
     static unsigned long long attr_done = 0;
-    auto kern = dwconv_lane_fwd_kernel<C::K_, C::S_, C::NCOL_, MODE, C::G_, KC>;
+    auto kern = dwconv_lane_fwd_kernel<C::K_, C::S_, C::NCOL_, MODE + (DWS ? 8 : 0), C::G_, KC>;
     constexpr int lds = MODE == 3 ? C::LDS_BYTES_FUSED : (MODE == 4 ? C::LDS_BYTES + KC * 2048 : (MODE == 5 ? C::LDS_BYTES_FUSED + KC * 2048 : C::LDS_BYTES));
     static_assert(lds <= 160 * 1024, "LDS budget");
     MC_SET_MAX_LDS(attr_done, kern, lds);
@@ -952,16 +971,31 @@ extern "C" int mc_dwconv_bwd_fused_lane(const mc_dwconv_args* a, void* stream) {
              "dwconv_bwd_fused: the BatchNorm-backward epilogue needs scale/shift/mean/invstd and stat_partials");
     MC_CHECK(!p.pro_scale, "dwconv_bwd_fused: dd carries no prologue");
     MC_CHECK(!(p.stat_rows > 0) || p.stat_rows == mc_dwconv_bwd_fused_lane_stat_rows(a), "dwconv_bwd_fused: stat_partials was sized for another configuration");
+    const int dw_rows = p.dw_partials ? mc_dwconv_bwd_fused_lane_stat_rows(a) : 0;
+    MC_CHECK(!(p.dw_partials && p.dw_rows > 0) || p.dw_rows == dw_rows, "dwconv_bwd_fused: dw_partials was sized for another configuration");
     hipStream_t st = (hipStream_t)stream;
+    int e;
     if (p.xw) {
         MC_CHECK(mc_aligned16(p.epi_x) && mc_aligned16(p.xw), "dwconv_bwd_fused (e from the block input): x / xw must be 16-byte aligned");
-        return lane::pick<3, 1, 5>(p, [&](auto cfg) {
+        e = lane::pick<3, 1, 5>(p, [&](auto cfg) {
             using Cf = decltype(cfg);
+            if (p.dw_partials) return p.cin <= 32 ? lane::launch<Cf, 5, 1, true>(p, st) : lane::launch<Cf, 5, 2, true>(p, st);
             if (p.cin <= 32) return lane::launch<Cf, 5, 1>(p, st);
             return lane::launch<Cf, 5, 2>(p, st);
         });
+    } else {
+        e = lane::pick<3, 1, 3>(p, [&](auto cfg) {
+            return p.dw_partials ? lane::launch<decltype(cfg), 3, 0, true>(p, st) : lane::launch<decltype(cfg), 3>(p, st);
+        });
     }
-    return lane::pick<3, 1, 3>(p, [&](auto cfg) { return lane::launch<decltype(cfg), 3>(p, st); });
+    if (e || !p.dw_partials) return e;
+    return mc_ordered_sum(p.dw_partials, dw_rows, (long long)p.k * p.k * p.c, (long long)p.k * p.k * p.c, p.dw_out, 1, stream);
+}
+// rows of dw_partials the fused launch writes: its y slots, the rows of stat_partials
+extern "C" int mc_dwconv_bwd_fused_dw_rows(const mc_dwconv_args* a) { return mc_dwconv_bwd_fused_lane_stat_rows(a); }
+extern "C" int mc_dwconv_bwd_weight_lane_dw_rows(const mc_dwconv_args* a) {
+    const mc_dwconv_args& p = *a;
+    return lane::pick_ks<2>(p, [&](auto cfg) { return lane::plan<decltype(cfg)>(p).ymax; });
 }
 
 // public names (include/mammoclip_hip.h).  _preferred: where the fused launch measured faster than the two launches it
@@ -986,7 +1020,12 @@ extern "C" int mc_dwconv_bwd_weight_lane(const mc_dwconv_args* a, void* stream) 
     MC_CHECK(mc_dwconv_lane_supported(a) && !p.epi_x, "dwconv_bwd_weight_lane: unsupported shape");
     MC_CHECK(p.x && p.dy && p.out, "dwconv_bwd_weight_lane: null x / dy / out");
     hipStream_t st = (hipStream_t)stream;
-    return lane::pick_ks<2>(p, [&](auto cfg) { return lane::launch<decltype(cfg), 2>(p, st); });
+    const int e = lane::pick_ks<2>(p, [&](auto cfg) {
+        return p.dw_partials ? lane::launch<decltype(cfg), 2, 0, true>(p, st) : lane::launch<decltype(cfg), 2>(p, st);
+    });
+    if (e || !p.dw_partials) return e;
+    return mc_ordered_sum(p.dw_partials, mc_dwconv_bwd_weight_lane_dw_rows(a), (long long)p.k * p.k * p.c, (long long)p.k * p.k * p.c,
+                          reinterpret_cast<float*>(p.out), 1, stream);
 }
 
 // ---- MODE 4: expand 1x1 conv + BatchNorm0 + swish inside the staging of the depthwise forward (include/mammoclip_hip.h)

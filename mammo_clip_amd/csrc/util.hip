@@ -290,6 +290,23 @@ __global__ void colsum_final_k(const float* __restrict__ partials, int rows, int
     out[i] = accumulate ? out[i] + (float)s : (float)s;
 }
 
+// out[i] (+)= (float) sum_r (double) ws[r * ld + i], r ascending: the finish step of the store-and-sum reductions (one fp64
+// accumulator per element, one rounding; four loads in flight, added in row order)
+__global__ __launch_bounds__(256) void ordered_sum_k(const float* __restrict__ ws, int rows, long long ld, long long n,
+                                                     float* __restrict__ out, int accumulate) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    int r = 0;
+    for (; r + 3 < rows; r += 4) {
+        const float a = ws[(long long)r * ld + i], b = ws[(long long)(r + 1) * ld + i];
+        const float d = ws[(long long)(r + 2) * ld + i], e = ws[(long long)(r + 3) * ld + i];
+        s += (double)a; s += (double)b; s += (double)d; s += (double)e;
+    }
+    for (; r < rows; ++r) s += (double)ws[(long long)r * ld + i];
+    out[i] = accumulate ? out[i] + (float)s : (float)s;
+}
+
 }  // namespace
 
 extern "C" int mc_cast_f32_bf16(const float* src, mc_bf16* dst, long long n, void* stream) {
@@ -411,6 +428,13 @@ extern "C" int mc_colsum_bf16(const mc_bf16* x, long long m, int c, long long ld
     MC_LAUNCH_CHECK();
     hipLaunchKernelGGL(colsum_final_k, dim3(mc_div_up(c, 16)), dim3(256), 0, (hipStream_t)stream, partials, rows, c,
                        out, accumulate);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_ordered_sum(const float* ws, int rows, long long ld, long long n, float* out, int accumulate, void* stream) {
+    MC_CHECK(ws && out, "ordered_sum: null pointer");
+    MC_CHECK(rows > 0 && n > 0 && ld >= n && n <= (1ll << 38), "ordered_sum: bad shape (rows > 0, 0 < n <= ld)");
+    hipLaunchKernelGGL(ordered_sum_k, dim3(mc_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, ws, rows, ld, n, out, accumulate);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

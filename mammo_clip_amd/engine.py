@@ -208,8 +208,12 @@ class LossScaler:
 class Trainer:
     def __init__(self, model, loss_func, optimizer, scheduler=None, device=None, bucket_mb: int = 256,
                  overlap_micro: bool = False, keep_graphs: int = 1, grad_sink: bool = True, keep_recompute: Optional[int] = None,
-                 stat_tapes: bool = True, loss_scale="auto", max_grad_norm: Optional[float] = None):
+                 stat_tapes: bool = True, loss_scale="auto", max_grad_norm: Optional[float] = None, deterministic: bool = False):
         self.model, self.loss_func, self.optimizer, self.scheduler = model, loss_func, optimizer, scheduler
+        # deterministic = True: ops.set_deterministic(True) for the duration of every step() (restored afterwards, also when the
+        # step raises): the backward runs without float atomics and two steps from the same state give the same bits.  Single
+        # process only -- at world size > 1 the order of the gradient all-reduce belongs to RCCL and nothing is promised.
+        self.deterministic = bool(deterministic)
         # gradient-norm clipping (torch.nn.utils.clip_grad_norm_ between unscale and step): None = off; a positive number
         # clips the rank-averaged gradients to that global L2 norm, float("inf") only reports the norm (``grad_norm``)
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -255,6 +259,7 @@ class Trainer:
             sync_parameters_and_buffers(model)
 
     def step(self, batch: Dict, micro_batches: int = 1) -> Dict[str, torch.Tensor]:
+        prev = ops.set_deterministic(True) if self.deterministic else None
         try:
             if micro_batches > 1:
                 return self._step_micro(batch, micro_batches)
@@ -262,6 +267,9 @@ class Trainer:
         except BaseException:
             self._abort_step()                  # no partial gradients / disarmed buckets survive into the next step
             raise
+        finally:
+            if prev is not None:
+                ops.set_deterministic(prev)
 
     def _abort_step(self):
         """a step that raised (OOM, a data error) leaves nothing behind: the sink with its partial gradients is dropped,

@@ -76,6 +76,7 @@ class DwconvArgs(C.Structure):
         ("epi_x", P), ("epi_scale", P), ("epi_shift", P), ("epi_mean", P), ("epi_invstd", P),
         ("dw_out", P), ("stat_rows", I),
         ("xw", P), ("cin", I),
+        ("dw_partials", P), ("dw_rows", I),
     ]
 
 
@@ -143,6 +144,9 @@ _SIGS = {
     "mc_dwconv_bwd_data_plan": ([C.POINTER(DwconvArgs), C.POINTER(C.c_int)], I),
     "mc_dwconv_bwd_data_xw_preferred": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_weight": ([C.POINTER(DwconvArgs), P], I),
+    "mc_dwconv_bwd_weight_dw_rows": ([C.POINTER(DwconvArgs)], I),
+    "mc_dwconv_bwd_data_dw_rows": ([C.POINTER(DwconvArgs)], I),
+    "mc_dwconv_bwd_fused_dw_rows": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_set_lane_mode": ([I], I),
     "mc_dwconv_lane_supported": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_fused_supported": ([C.POINTER(DwconvArgs)], I),
@@ -174,6 +178,11 @@ _SIGS = {
     "mc_bert_embed_bwd": ([P, P, P, P, P, P, P, P, P, I, I, I, F, ULL, U, P, P, P, P, P, P], I),
     "mc_add_ln_fwd": ([P, P, P, P, F, LL, I, F, ULL, U, P, P, P, P], I),
     "mc_add_ln_bwd": ([P, P, P, P, P, P, LL, I, F, ULL, U, P, P, P, P, P], I),
+    "mc_add_ln_bwd_ws_rows": ([LL], I),
+    "mc_add_ln_bwd_ws": ([P, P, P, P, P, P, LL, I, F, ULL, U, P, P, P, P, P, I, P], I),
+    "mc_bert_embed_bwd_ws_floats": ([I, I, I, LL, C.POINTER(C.c_int)], LL),
+    "mc_bert_embed_bwd_ws": ([P, P, P, P, P, P, P, P, P, I, I, I, F, ULL, U, P, P, P, P, P, P, P, P, LL, P], I),
+    "mc_ordered_sum": ([P, I, LL, LL, P, I, P], I),
     "mc_softmax_fwd": ([P, LL, I, F, ULL, U, P, P, P], I),
     "mc_softmax_bwd": ([P, P, LL, I, F, ULL, U, F, P, P], I),
     "mc_bn_fold_prepare": ([P, P, P, P, D, I, I, P, P, P, P], I),
@@ -194,6 +203,8 @@ _SIGS = {
     "mc_bert_embed_rows_bwd": ([P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, ULL, U, P, P, P, P, P, P], I),
     "mc_add_ln_rows_fwd": ([P, P, P, P, P, F, LL, I, F, ULL, U, P, P, P, P], I),
     "mc_add_ln_rows_bwd": ([P, P, P, P, P, P, P, LL, I, F, ULL, U, P, P, P, P, P], I),
+    "mc_bert_embed_rows_bwd_ws": ([P, P, P, P, P, P, P, P, P, P, I, I, I, I, LL, F, ULL, U, P, P, P, P, P, P, P, P, LL, P], I),
+    "mc_add_ln_rows_bwd_ws": ([P, P, P, P, P, P, P, LL, I, F, ULL, U, P, P, P, P, P, I, P], I),
     "mc_rows_gather": ([P, P, I, I, P, P], I),
     "mc_rows_scatter": ([P, P, I, I, P, P], I),
     "mc_segment_mean_fwd": ([P, P, I, I, P, P], I),

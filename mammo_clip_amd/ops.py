@@ -32,6 +32,42 @@ def _st():
     return _RAW_STREAM(_GET_DEV())
 
 
+# ---------------------------------------------------------------------------------------- deterministic mode
+# Opt-in: the backward scatter-adds that end in float atomics by default (depthwise weight gradients, LayerNorm gamma / beta,
+# the embedding tables) take their store-and-sum endings instead -- per-unit partial rows in a workspace, summed in row order by
+# a second launch on the same stream (include/mammoclip_hip.h: dw_partials, mc_*_bwd_ws, mc_ordered_sum).  Two steps from the
+# same state then give the same bits.  Single process only: at world size > 1 the all-reduce order belongs to RCCL.
+_DETERMINISTIC = os.environ.get("MC_DETERMINISTIC", "0") not in ("", "0")
+
+
+def deterministic():
+    return _DETERMINISTIC
+
+
+def set_deterministic(flag):
+    """switch the store-and-sum endings on / off; returns the previous value"""
+    global _DETERMINISTIC
+    prev, _DETERMINISTIC = _DETERMINISTIC, bool(flag)
+    return prev
+
+
+def _dw_partials(a, rows_fn, like):
+    """deterministic mode: the weight-gradient workspace of the depthwise launch described by ``a`` (kept alive by the caller)"""
+    if not _DETERMINISTIC:
+        return None
+    rows = getattr(L.load(), rows_fn)(C.byref(a))
+    ws = torch.empty((rows, a.k * a.k, a.c), dtype=torch.float32, device=like.device)
+    a.dw_partials, a.dw_rows = _p(ws), rows
+    return ws
+
+
+def token_rows_by_id(ids):
+    """inverted index of a token batch for the store-and-sum embedding backward: (sorted_ids, order), the flattened ids sorted
+    ascending by a STABLE sort and the token row of each sorted entry -- the rows of one id are adjacent and ascending"""
+    sorted_ids, order = torch.sort(ids.reshape(-1), stable=True)
+    return sorted_ids.contiguous(), order.contiguous()
+
+
 # ---------------------------------------------------------------------------------------- side streams
 # The three encoder calls of one BreastClip.forward (view 1, view 2, both reports) are independent until the projection heads
 # [ref: model/clip.py:83-108]; model/clip.py can issue them on separate HIP streams so the latency-bound launches of one chain
@@ -681,6 +717,7 @@ def _dwconv_bwd_data_impl(dy, w_kkc, n, h, w, c, k, stride, pad_l, pad_t, oh, ow
         if dw:
             dwdw = torch.zeros((k * k, c), dtype=torch.float32, device=dy.device)
             a.dw_out = _p(dwdw)
+            ws = _dw_partials(a, "mc_dwconv_bwd_data_dw_rows", dy)  # noqa: F841  (alive until the launch is queued)
         _note(2 * n * (c * (oh * ow + h * w) + cin * h * w), (4 if dw else 2) * n * c * oh * ow * k * k + 2 * n * h * w * c * cin)
         L.call("mc_dwconv_bwd_data", C.byref(a), _st(), kind=f"k{k}s{stride}|dgrad_bn|x")
         return (dz, part, dwdw) if dw else (dz, part)
@@ -765,6 +802,7 @@ def dwconv_bwd_fused(dd, e, st, w_kkc_flipped, n, h, w, c, k, pad_l, pad_t, oh, 
     rows = L.load().mc_dwconv_bwd_fused_stat_rows(C.byref(a))
     part = empty((rows, 2, c), torch.float32, dd)
     a.out, a.dw_out, a.stat_partials, a.stat_rows = _p(dz), _p(dw), _p(part), rows
+    ws = _dw_partials(a, "mc_dwconv_bwd_fused_dw_rows", dd)  # noqa: F841  (alive until the launch is queued)
     if xw is None:
         _note(2 * n * c * (oh * ow + 2 * h * w), 4 * n * c * h * w * k * k)
     else:
@@ -832,6 +870,7 @@ def _dwconv_bwd_weight_impl(x, dy, n, h, w, c, k, stride, pad_l, pad_t, oh, ow, 
     a.x, a.dy, a.out = _p(x), _p(dy), _p(dw)
     if pro is not None:
         a.pro_scale, a.pro_shift = _p(pro[0]), _p(pro[1])
+    ws = _dw_partials(a, "mc_dwconv_bwd_weight_dw_rows", x)  # noqa: F841  (alive until the launch is queued)
     _note(2 * n * c * (h * w + oh * ow), 2 * n * c * oh * ow * k * k)
     L.call("mc_dwconv_bwd_weight", C.byref(a), _st(), kind=f"k{k}s{stride}")
     return dw
@@ -1077,6 +1116,20 @@ def bert_embed_bwd(dy, ids, tt, word, pos, typ, gamma, mean, rstd, p, seed, sid,
     h = word.shape[1]
     dword, dpos, dtyp = torch.zeros_like(word), torch.zeros_like(pos), torch.zeros_like(typ)
     dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
+    if _DETERMINISTIC:
+        b, t, rows = (ids.shape[0], ids.shape[1], ids.numel()) if pk is None else (pk.b, pk.max_len, pk.real)
+        sorted_ids, order = token_rows_by_id(ids.reshape(-1)[:rows])
+        nfl = L.load().mc_bert_embed_bwd_ws_floats(b, t, h, rows, None)
+        ws = torch.empty((nfl,), dtype=torch.float32, device=word.device)
+        tail = (float(p), int(seed), int(sid), _p(dword), _p(dpos), _p(dtyp), _p(dgamma), _p(dbeta), _p(sorted_ids), _p(order),
+                _p(ws), nfl, _st())
+        if pk is None:
+            L.call("mc_bert_embed_bwd_ws", _p(dy), _p(ids), _p(tt), _p(word), _p(pos), _p(typ), _p(gamma), _p(mean), _p(rstd), b, t,
+                   h, *tail)
+        else:
+            L.call("mc_bert_embed_rows_bwd_ws", _p(dy), _p(ids), _p(tt), _p(pk.cu), _p(word), _p(pos), _p(typ), _p(gamma), _p(mean),
+                   _p(rstd), pk.b, pk.max_len, pk.t, h, rows, *tail)
+        return dword, dpos, dtyp, dgamma, dbeta
     tail = (h, float(p), int(seed), int(sid), _p(dword), _p(dpos), _p(dtyp), _p(dgamma), _p(dbeta), _st())
     if pk is None:
         b, t = ids.shape
@@ -1105,8 +1158,13 @@ def add_ln_bwd(dy, x, res, gamma, mean, rstd, p, seed, sid, row_map=None):
     gb = torch.zeros((2,) + tuple(gamma.shape), dtype=gamma.dtype, device=gamma.device)
     dgamma, dbeta = gb[0], gb[1]
     name, rm = ("mc_add_ln_bwd", ()) if row_map is None else ("mc_add_ln_rows_bwd", (_p(row_map),))
+    wsa = ()
+    if _DETERMINISTIC:
+        wr = L.load().mc_add_ln_bwd_ws_rows(rows)
+        ws = torch.empty((wr, 2, h), dtype=torch.float32, device=x.device)
+        name, wsa = name + "_ws", (_p(ws), wr)
     L.call(name, _p(dy), _p(x), _p(res), *rm, _p(gamma), _p(mean), _p(rstd), rows, h, float(p), int(seed), int(sid), _p(dx),
-           _p(dres), _p(dgamma), _p(dbeta), _st())
+           _p(dres), _p(dgamma), _p(dbeta), *wsa, _st())
     return dx, dres, dgamma, dbeta
 
 
