@@ -363,6 +363,11 @@ int mc_bn_finalize(const float* partials, int rows, int c, double count, const f
 /* eval mode: scale/shift from running statistics */
 int mc_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                       const float* running_var, float eps, int c, float* scale, float* shift, void* stream);
+/* the same, with the two rows a BACKWARD through a BatchNorm on running statistics needs as well (frozen BatchNorm:
+ * model.eval() with autograd on, or EfficientNet.freeze_bn): mean = running_mean, invstd = 1/sqrt(running_var + eps);
+ * scale / shift by the very fp32 expressions of mc_bn_eval_coeffs (bit-identical).  All outputs float[c]. */
+int mc_bn_eval_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                     float eps, int c, float* mean, float* invstd, float* scale, float* shift, void* stream);
 
 /* elementwise family on x[n_img * hw, c] (bf16):  z = x*scale[c] + shift[c];  y = act(z)  (act 0 none, 1 SiLU)
  * apply:  out = y * rowscale[img] + res            (rowscale = drop_connect keep/keep_prob, res = skip input)
@@ -407,6 +412,11 @@ int mc_bnact_apply(const mc_bnact_args* args, void* stream);
 int mc_bnact_pool(const mc_bnact_args* args, void* stream);
 int mc_bnact_bwd_reduce(const mc_bnact_args* args, void* stream);
 int mc_bnact_bwd_apply(const mc_bnact_args* args, void* stream);
+/* Backward through a FROZEN BatchNorm (running statistics) in ONE pass: the reduce pass (same optional g / mul / add /
+ * add_scale / rowscale, act 0 / 1, same grid, same partials layout with mc_bnact_rows() rows, same reduction order: no atomics)
+ * that also stores dx = scale[c] * dz (16 bit; required) -- frozen, dx does not depend on the reduction.  mean / invstd are the
+ * running statistics (mc_bn_eval_stats); partials go to mc_bn_bwd_finalize_frozen for dgamma / dbeta. */
+int mc_bnact_bwd_frozen(const mc_bnact_args* args, void* stream);
 int mc_bnact_se_dgate(const mc_bnact_args* args, void* stream);
 /* one pass over (x, g): args->dgate = float[5][n_img][c]: {sum g*y, sum g*y', sum g*y'*xhat, sum y', sum y'*xhat}
  * (y = act(z)); [0] is d loss / d gate, [1..4] let the BatchNorm-backward sums be formed without another pass: */
@@ -418,6 +428,15 @@ int mc_bn_partials_from_se_sums(const float* sums, const float* gate, const floa
 int mc_bn_bwd_finalize(const float* partials, int rows, int c, double count, const float* gamma,
                        const float* mean, const float* invstd, float* dgamma, float* dbeta, float* coef,
                        void* stream);
+/* frozen BatchNorm: the same fp64 reduction of partials[rows][2][c] (xhat from the running statistics) -> dgamma, dbeta;
+ * coef[3][c] = (scale, 0, 0) exactly, so every apply-type consumer (mc_bnact_bwd_apply, gemm_rows epi_mode 2) computes the
+ * frozen dx = scale*dz unchanged */
+int mc_bn_bwd_finalize_frozen(const float* partials, int rows, int c, const float* scale, float* dgamma, float* dbeta,
+                              float* coef, void* stream);
+/* frozen BatchNorm in front of a 1x1 conv e = x W^T (W = src [n, k] fp32): de = diag(scale) dz, hence dx = dz (diag(scale) W)
+ * and dW = diag(scale) (dz^T x).  Row i of src times scale[i], written as w_t [k, n] (16 bit, TRANSPOSED: the data-gradient
+ * GEMM's operand) and / or as out [n, k] fp32 (may alias src); either output may be NULL, not both. */
+int mc_bn_frozen_rows(const float* src, const float* scale, int n, int k, mc_bf16* w_t, float* out, void* stream);
 
 /* Training-mode BatchNorm backward folded into the 1x1 convolution in front of it (bnfold.hip; MBConv expand conv +
  * _bn0 [ref: efficientnet_custom.py:104-107]): with e = x We^T (We [n, k] fp32), coef = (A, B, C) from

@@ -124,6 +124,15 @@ class BreastClip(nn.Module):
             self.logit_scale = torch.tensor(1, dtype=torch.float32)
             log.warning("[Mammo-CLIP] missing temperature scaling factor")
 
+    def freeze_bn(self, on: bool = True):
+        """image encoder's BatchNorm sites on their running statistics, in train() mode too (EfficientNet.freeze_bn); returns self"""
+        self.image_encoder.freeze_bn(on)
+        return self
+
+    @property
+    def frozen_bn(self) -> bool:
+        return bool(getattr(self.image_encoder, "frozen_bn", False))
+
     def encode_image(self, image):
         feats = self.image_encoder(image)
         if self.model_config["image_encoder"]["model_type"].lower() == "cnn":

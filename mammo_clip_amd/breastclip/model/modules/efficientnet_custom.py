@@ -204,6 +204,12 @@ def _conv_stats(fn, training, *a, stats=True, **kw):
     return fn(*a, stats=True, **kw)
 
 
+def _no_fp8_frozen(mod):
+    if mod.fp8:
+        raise NotImplementedError("backward through BatchNorm on running statistics (eval mode / freeze_bn) is not implemented "
+                                  "for the fp8 forward (set_fp8)")
+
+
 # expanded-tensor bytes per call from which the BatchNorm0 backward is folded into the expand conv's gradient GEMMs
 # (ops.bn_fold_expand_bwd) instead of running the apply pass; tests set it to 0 to exercise the folded path at small sizes
 LINK_STEM = os.environ.get("MC_LINK_STEM", "1") != "0"                  # stem bn0 + swish inside block 0's depthwise kernels (_StemLink)
@@ -235,10 +241,10 @@ class _StemFn(torch.autograd.Function):
         c0 = w.shape[0]
         patches = ops.stem_im2col(x, l, t, oh, ow)
         wb = ops.stem_weight_prep(w)
-        training = mod.training
+        training = mod.batch_stats
         e, part = _conv_stats(ops.linear_fwd, training, patches, wb)
         st = _bn_stats(part, n * oh * ow, mod._bn0, training)
-        ctx.mod, ctx.st, ctx.geo = mod, st, (n, h, wd, oh, ow, c0)
+        ctx.mod, ctx.st, ctx.geo, ctx.frozen = mod, st, (n, h, wd, oh, ow, c0), not training
         ctx.raw = (x.mean, x.std) if isinstance(x, ops.RawImages) else None
         ctx.save_for_backward(x.data if ctx.raw else x, e)
         ctx.link = link
@@ -255,7 +261,16 @@ class _StemFn(torch.autograd.Function):
         n, h, wd, oh, ow, c0 = ctx.geo
         mod = ctx.mod
         link = ctx.link
-        if link is not None:
+        if ctx.frozen:
+            _no_fp8_frozen(mod)
+        if ctx.frozen and link is not None:
+            # frozen bn0: de = scale0 * dZ0 is never formed -- the conv's weight gradient is taken from dZ0 and row-scaled
+            de = dy.contiguous()
+            _, dgamma, dbeta = ops.bn_bwd_coefs(link.part, 0, ctx.st, mod._bn0.weight, frozen=True)
+            link.part = None
+        elif ctx.frozen:
+            de, dgamma, dbeta = ops.bnact_bwd(e, n, oh * ow, c0, ctx.st, mod._bn0.weight, 1, g=dy.contiguous(), frozen=True)
+        elif link is not None:
             # dy is already dZ0 = dL/d bn0(e) (block 0's data-gradient epilogue), link.part its BatchNorm-backward reductions
             de, dgamma, dbeta = ops.bnact_bwd(e, n, oh * ow, c0, ctx.st, mod._bn0.weight, 0, g=dy.contiguous(), partials=link.part)
             link.part = None
@@ -264,6 +279,8 @@ class _StemFn(torch.autograd.Function):
         l, r, t, b = mod.stem_pad
         patches = ops.stem_im2col(x, l, t, oh, ow)                 # recomputed, not stored
         dw = ops.linear_wgrad(de, patches)                         # [c0, 32]
+        if ctx.frozen and link is not None:
+            dw = ops.rowscale_f32_(dw, ctx.st.scale)
         gw, gg, gb = ops.deliver_param_grads((mod._conv_stem.weight, mod._bn0.weight, mod._bn0.bias),
                                              (dw[:, :27].reshape(c0, 3, 3, 3), dgamma, dbeta))
         return (None, gw, gg, gb, None) + ((None,) if link is not None else ())
@@ -285,7 +302,7 @@ def _expand_conv(pl, x, we, stats=True):
         # config #5: fp8 (e4m3, per-tensor scale) activations and weights on the fp8 MFMA; BatchNorm statistics
         # and everything downstream stay on the bf16 / fp32 path; backward uses the bf16 tensors (straight-through)
         return ops.linear_fwd_fp8(x, we, stats=True)
-    return _conv_stats(ops.linear_fwd, pl.training, x, we, stats=stats)
+    return _conv_stats(ops.linear_fwd, pl.batch_stats, x, we, stats=stats)
 
 
 def _depthwise(blk, pl, x, e, we, wkkc, pro0, stats=True):
@@ -293,8 +310,8 @@ def _depthwise(blk, pl, x, e, we, wkkc, pro0, stats=True):
     depthwise launch: from the UNROUNDED expand output) or from e / the linked stem output x (pro0 = the BatchNorm0 + swish
     prologue).  The backward rebuilds d through this very function (stats=False): same launch, bit for bit."""
     if pl.xdw:
-        return _conv_stats(ops.mbconv_xdw_fwd, pl.training, x, we, pro0, wkkc, *pl.dw, stats=stats)
-    return _conv_stats(ops.dwconv_fwd, pl.training, e if blk.args.expand != 1 else x, wkkc, *pl.dw, stats=stats, pro=pro0)
+        return _conv_stats(ops.mbconv_xdw_fwd, pl.batch_stats, x, we, pro0, wkkc, *pl.dw, stats=stats)
+    return _conv_stats(ops.dwconv_fwd, pl.batch_stats, e if blk.args.expand != 1 else x, wkkc, *pl.dw, stats=stats, pro=pro0)
 
 
 def _project_conv(pl, d, act1, st1, gate, wp, stats=True):
@@ -305,7 +322,7 @@ def _project_conv(pl, d, act1, st1, gate, wp, stats=True):
         return ops.linear_fwd_fp8(act1, wg, stats=True, batch_w=(pl.n, ohw))
     # stored activation: only the SE gate is applied; else BN1 + SiLU + gate while the GEMM stages its A operand
     src, pro = (act1, (None, None, gate, ohw)) if pl.keep_act else (d, (st1.scale, st1.shift, gate, ohw))
-    return _conv_stats(ops.linear_fwd, pl.training, src, wp, stats=stats, pro=pro)
+    return _conv_stats(ops.linear_fwd, pl.batch_stats, src, wp, stats=stats, pro=pro)
 
 
 class _MBConvFn(torch.autograd.Function):
@@ -316,7 +333,9 @@ class _MBConvFn(torch.autograd.Function):
     def forward(ctx, x, rowscale, blk, n, h, w, recording, link, *params):
         a = blk.args
         pl = blk.plan(n, h, w, recording)
-        training, ohw = pl.training, pl.oh * pl.ow
+        # bstat: BatchNorm on batch statistics (statistics epilogues, finalize launches, their tape entries); training: the module's
+        # mode -- the stochastic pieces and the tape entries of the squeeze-excite values (frozen BatchNorm: bstat off, training on)
+        training, bstat, ohw = pl.training, pl.batch_stats, pl.oh * pl.ow
         wkkc = blk.w_taps()
         e = we = st0 = gram = None
         if a.expand != 1:
@@ -326,9 +345,9 @@ class _MBConvFn(torch.autograd.Function):
                 # over x, 6 x narrower than e), from the statistics tape of a re-forward, or from the running statistics (eval).
                 # x^T x and colsum(x) of the Gram statistics pass are what the folded BatchNorm0 backward of this block needs
                 # again: they stay in the graph (a few KB) and travel on the statistics tape to the re-forward's backward
-                if training and _replaying():
+                if bstat and _replaying():
                     part0, gram = None, _TAPE.get()
-                elif training:
+                elif bstat:
                     part0, gram = ops.bn_gram_partials(x, we, n * h * w)
                     if _TAPE is not None:
                         _TAPE.put(gram)
@@ -336,13 +355,13 @@ class _MBConvFn(torch.autograd.Function):
                     part0 = None
             else:
                 e, part0 = _expand_conv(pl, x, we)
-            st0 = _bn_stats(part0, n * h * w, blk._bn0, training)
+            st0 = _bn_stats(part0, n * h * w, blk._bn0, bstat)
             pro0 = (st0.scale, st0.shift)
         else:
             # block 0 behind a linked stem: x is the stem's RAW conv output, its bn0 + swish is this block's prologue
             pro0 = (link.st.scale, link.st.shift) if link is not None else None
         d, part1 = _depthwise(blk, pl, x, e, we, wkkc, pro0)
-        st1 = _bn_stats(part1, n * ohw, blk._bn1, training)
+        st1 = _bn_stats(part1, n * ohw, blk._bn1, bstat)
         # Late stages (project conv on the tiled GEMM): the squeeze pass also stores A = silu(bn1(d)); the project GEMM
         # and its weight gradient then apply only the SE gate instead of re-evaluating BN+SiLU per output tile.
         if pl.keep_act:
@@ -362,7 +381,7 @@ class _MBConvFn(torch.autograd.Function):
                 _TAPE.put(gate)
         wp = blk.w_project()
         p, part2 = _project_conv(pl, d, act1, st1, gate, wp)
-        st2 = _bn_stats(part2, n * ohw, blk._bn2, training)
+        st2 = _bn_stats(part2, n * ohw, blk._bn2, bstat)
         y = ops.bnact_apply(p, n, ohw, a.cout, st2.scale, st2.shift, 0,
                             rowscale=rowscale if a.skip else None, res=x if a.skip else None)
         # what the plan does not store (recompute modes, see EfficientNet.set_recompute) the backward rebuilds from the block
@@ -383,6 +402,10 @@ class _MBConvFn(torch.autograd.Function):
         dy = dy.contiguous()
         x, e, d, p, act1, link, pro0 = sv["x"], sv["e"], sv["d"], sv["p"], sv["act1"], sv["link"], sv["pro0"]
         st0, st1, st2, gate, pooled = sv["st0"], sv["st1"], sv["st2"], sv["gate"], sv["pooled"]
+        # frozen BatchNorm (running statistics): dx = scale*dz at every site, the reductions only feed dgamma / dbeta
+        frozen = not pl.batch_stats
+        if frozen:
+            _no_fp8_frozen(blk)
         if a.expand != 1 and e is None and not (pl.efree or pl.efree_s2):     # (recompute modes: same kernels, statistics epilogues off)
             e = _expand_conv(pl, x, sv["we"], stats=False)[0]
         if d is None:
@@ -392,7 +415,7 @@ class _MBConvFn(torch.autograd.Function):
         if p is None:                                        # mode 4: the projection conv again, from the rebuilt d
             p = _project_conv(pl, d, act1, st1, gate, sv["wp"], stats=False)[0]
         # y = bn2(p) * rowscale + x
-        dp, dg2, db2 = ops.bnact_bwd(p, n, ohw, a.cout, st2, blk._bn2.weight, 0, g=dy, rowscale=sv["rowscale"])
+        dp, dg2, db2 = ops.bnact_bwd(p, n, ohw, a.cout, st2, blk._bn2.weight, 0, g=dy, rowscale=sv["rowscale"], frozen=frozen)
         # project 1x1: p = A1 . wp^T, A1 = silu(bn1(d)) * gate   (A1 is recomputed inside the wgrad GEMM)
         wp_t = blk.w_project(transposed=True)                # [cexp, cout]
         # Early stages (row-streaming shapes, whole 16-row groups per image): dA1 = dp . wp never goes to memory -- the
@@ -414,11 +437,11 @@ class _MBConvFn(torch.autograd.Function):
         # bn1 + swish: upstream of swish output = dA1 * gate + dpooled / (oh*ow)
         part1 = ops.bn_partials_from_se_sums(sums, gate, dpooled, 1.0 / ohw)
         if pl.fuse_proj_dgrad:
-            coef1, dg1, db1n = ops.bn_bwd_coefs(part1, n * ohw, st1, blk._bn1.weight)
+            coef1, dg1, db1n = ops.bn_bwd_coefs(part1, n * ohw, st1, blk._bn1.weight, frozen=frozen)
             dd = ops.proj_dgrad_bn_apply(dp, wp_t, d, st1, coef1, gate, dpooled, 1.0 / ohw, ohw)
         else:
             dd, dg1, db1n = ops.bnact_bwd(d, n, ohw, a.cexp, st1, blk._bn1.weight, 1, g=da1, mul=gate, add=dpooled,
-                                          add_scale=1.0 / ohw, partials=part1)
+                                          add_scale=1.0 / ohw, partials=part1, frozen=frozen)
         del da1
         # depthwise
         del d
@@ -446,7 +469,20 @@ class _MBConvFn(torch.autograd.Function):
             else:
                 dz0, part0 = ops.dwconv_bwd_data(dd, sv["wkkc"], *pl.dw, w_kkc_flipped=wflip, epi=(e, st0))
             del dd
-            if pl.fold_bn0:
+            if frozen:
+                # de = scale0 * dZ0 is never formed: dx = dZ0 (diag(scale0) We) through a 16-bit image of the row-scaled weight,
+                # dWe = diag(scale0) (dZ0^T x) -- no pass over an expanded-size tensor beyond the two GEMMs' read of dZ0
+                del e, dw_in
+                _, dg0, db0 = ops.bn_bwd_coefs(part0, n * hw, st0, blk._bn0.weight, frozen=True)
+                ws_t = ops.bn_frozen_weight_t(blk._expand_conv.weight.view(a.cexp, a.cin), st0.scale)      # [cin, cexp]
+                if pl.xbwd:
+                    dx, dwe = ops.xbwd_rows(dz0, x, ws_t, residual=dy if a.skip else None)
+                else:
+                    dx = ops.linear_dgrad(dz0, sv["we"], residual=dy if a.skip else None, w_t=ws_t)
+                    dwe = ops.linear_wgrad(dz0, x)
+                dwe = ops.rowscale_f32_(dwe, st0.scale)
+                de = None
+            elif pl.fold_bn0:
                 # bn0 backward is linear in (dZ0, e) and e = x We^T: it is folded into the operands of the expand conv's
                 # two gradient GEMMs (ops.bn_fold_expand_bwd) -- de is never formed, e is not read again.  Three passes
                 # over the expanded tensor against ~10 small launches and 6 passes over the (6x smaller) block input:
@@ -503,10 +539,10 @@ class _HeadFn(torch.autograd.Function):
         if mod.fp8 and cin % 16 == 0:
             e, part = ops.linear_fwd_fp8(x, wb, stats=True)
         else:
-            e, part = _conv_stats(ops.linear_fwd, mod.training, x, wb)
-        st = _bn_stats(part, n * h * wd, mod._bn1, mod.training)
+            e, part = _conv_stats(ops.linear_fwd, mod.batch_stats, x, wb)
+        st = _bn_stats(part, n * h * wd, mod._bn1, mod.batch_stats)
         pooled = ops.bnact_pool(e, n, h * wd, cout, st.scale, st.shift, 1)
-        ctx.mod, ctx.st, ctx.geo = mod, st, (n, h, wd, cin, cout)
+        ctx.mod, ctx.st, ctx.geo, ctx.frozen = mod, st, (n, h, wd, cin, cout), not mod.batch_stats
         ctx.save_for_backward(x, e, wb)
         mod._head_cache = (e, st, n, h, wd, cout)
         return pooled
@@ -516,8 +552,10 @@ class _HeadFn(torch.autograd.Function):
         x, e, wb = ctx.saved_tensors
         n, h, wd, cin, cout = ctx.geo
         mod = ctx.mod
+        if ctx.frozen:
+            _no_fp8_frozen(mod)
         de, dgamma, dbeta = ops.bnact_bwd(e, n, h * wd, cout, ctx.st, mod._bn1.weight, 1, add=dpooled.contiguous(),
-                                          add_scale=1.0 / (h * wd))
+                                          add_scale=1.0 / (h * wd), frozen=ctx.frozen)
         dx = ops.linear_dgrad(de, wb, w_t=ops.cast_transpose_bf16(mod._conv_head.weight.view(cout, cin)))
         dw = ops.linear_wgrad(de, x)
         gw, gg, gb = ops.deliver_param_grads((mod._conv_head.weight, mod._bn1.weight, mod._bn1.bias),
@@ -567,7 +605,11 @@ class _Conv(nn.Conv2d):
 _Geo = namedtuple("_Geo", ["idx", "expand", "k", "s", "cin", "cexp", "cout", "cse", "pad", "skip"])
 # one call of an MBConv block (MBConvBlock.plan); dw = (n, h, w, cexp, k, s, pad_l, pad_t, oh, ow), the argument run of ops.dwconv_*
 _Plan = namedtuple("_Plan", ["n", "h", "w", "oh", "ow", "training", "xdw", "efree", "fp8_expand", "keep_act", "fp8_project",
-                             "store_e", "store_d", "store_p", "fuse_proj_dgrad", "fused_dw", "fold_bn0", "xbwd", "dw", "efree_s2"])
+                             "store_e", "store_d", "store_p", "fuse_proj_dgrad", "fused_dw", "fold_bn0", "xbwd", "dw", "efree_s2",
+                             "batch_stats"])
+# training: the module's mode (stochastic pieces, the statistics tape's squeeze-excite entries); batch_stats: BatchNorm on batch
+# statistics = training and not frozen (statistics epilogues, finalize, running-statistic updates, Gram pairs and every path whose
+# backward reads them).  Frozen (batch_stats off) the backward is the running-statistics one: dx = scale*dz at every site
 
 
 class MBConvBlock(nn.Module):
@@ -596,9 +638,15 @@ class MBConvBlock(nn.Module):
                          bool(a.id_skip and s == 1 and cin == a.output_filters))
         self._param_names = [n for n, _ in self.named_parameters()]
         self.fp8 = False
+        self.frozen_bn = False            # EfficientNet.freeze_bn
         self.recompute = 0
         self.register_buffer("_ones", torch.ones(cin), persistent=False)
         self.register_buffer("_zeros", torch.zeros(cin), persistent=False)
+
+    @property
+    def batch_stats(self):
+        """do this block's BatchNorm layers use (and update from) batch statistics?  Otherwise: the running statistics"""
+        return self.training and not self.frozen_bn
 
     def out_geo(self, n, h, w):
         """(n, oh, ow) of this block's output for an (n, h, w) input"""
@@ -622,7 +670,7 @@ class MBConvBlock(nn.Module):
         Grad mode is only a proxy for "e must be stored": under ``torch.utils.checkpoint`` (first pass under no_grad, recompute
         with grad on) the two passes would take different forwards and differ in the last bits.  Such a caller first sets
         recompute mode >= 1 on the ``xdw_capable`` blocks, as ``EfficientNet.xdw_reforward_modes`` does for the micro-batched step."""
-        a, rc, expand = self.args, self.recompute, self.args.expand != 1
+        a, rc, expand, bstat = self.args, self.recompute, self.args.expand != 1, self.batch_stats
         _, oh, ow = self.out_geo(n, h, w)
         rows, orows = n * h * w, n * oh * ow
         dw = (n, h, w, a.cexp, a.k, a.s, a.pad[0], a.pad[2], oh, ow)
@@ -630,7 +678,9 @@ class MBConvBlock(nn.Module):
         # stride-1 3x3 blocks whose backward forms its e rows from x as well (ops.dwconv_bwd_fused with xw) and folds the
         # BatchNorm0 backward into the expand conv's gradient GEMMs never need e anywhere: an E-free plan IS fused forward +
         # fused depthwise backward + fold (enough expanded bytes for the fold to be the chosen BatchNorm0 backward)
-        efree = bool(fusable and ops.EFREE and FUSE_DW_BWD and a.k == 3 and a.s == 1 and self.training
+        # (batch statistics only: both E-free forms fold BatchNorm0 through the forward's Gram pair, which a frozen forward -- running
+        # statistics -- does not produce; the frozen BatchNorm0 backward needs neither fold nor Gram pair, see _MBConvFn.backward)
+        efree = bool(fusable and ops.EFREE and FUSE_DW_BWD and a.k == 3 and a.s == 1 and bstat
                      and 2 * rows * a.cexp >= BN_FOLD_MIN_BYTES and ops.dwconv_bwd_fused_ok(*dw, cin=a.cin))
         # ... and where no backward needs e stored (no graph, or a recompute mode that rebuilds it) the forward is fused too
         xdw = efree or (fusable and (rc >= 1 or not recording))
@@ -639,17 +689,18 @@ class MBConvBlock(nn.Module):
         if recording:
             fuse_proj = bool(FUSE_PROJ_DGRAD and ops.proj_dgrad_fusable(orows, a.cexp, a.cout, oh * ow))
             fused_dw = efree or bool(FUSE_DW_BWD and expand and ops.dwconv_bwd_fused_ok(*dw))
-            fold = expand and (efree or 2 * rows * a.cexp >= (BN_FOLD_MIN_BYTES if a.s == 1 else max(BN_FOLD_MIN_BYTES, BN_FOLD_S2_MIN_BYTES)))
+            fold = expand and bstat and (efree or 2 * rows * a.cexp >= (BN_FOLD_MIN_BYTES if a.s == 1 else max(BN_FOLD_MIN_BYTES, BN_FOLD_S2_MIN_BYTES)))
             xbwd = expand and not fold and ops.xbwd_rows_ok(rows, a.cexp, a.cin)
         # stride-2 3x3 blocks whose e is not stored (recompute modes >= 1): the backward forms the e rows from x inside the data-
         # gradient launch, which is the weight gradient too (ops.dwconv_bwd_data with xw), and folds BatchNorm0: e is not rebuilt
-        efree_s2 = bool(recording and fusable and ops.EFREE_S2 and a.k == 3 and a.s == 2 and self.training and rc >= 1 and fold
+        efree_s2 = bool(recording and fusable and ops.EFREE_S2 and a.k == 3 and a.s == 2 and bstat and rc >= 1 and fold
                         and ops.dwconv_bwd_s2_xw_ok(*dw, cin=a.cin, force=ops.EFREE_S2 >= 2))
         return _Plan(n, h, w, oh, ow, self.training, xdw, efree,
                      fp8_expand=bool(expand and self.fp8 and a.cin % 16 == 0 and not ops._rows_ok(rows, a.cexp, a.cin, None, 0)),
                      keep_act=keep_act, fp8_project=keep_act and self.fp8 and a.cexp % 16 == 0 and a.cout > 64,
                      store_e=expand and rc == 0 and not xdw, store_d=rc < 2, store_p=rc < 4,
-                     fuse_proj_dgrad=fuse_proj, fused_dw=fused_dw, fold_bn0=fold, xbwd=xbwd, dw=dw, efree_s2=efree_s2)
+                     fuse_proj_dgrad=fuse_proj, fused_dw=fused_dw, fold_bn0=fold, xbwd=xbwd, dw=dw, efree_s2=efree_s2,
+                     batch_stats=bstat)
 
     def w_expand(self, transposed=False):
         """cached 16-bit image of the expand conv's weight, [cexp, cin] or transposed.  (Forward, backward and
@@ -724,6 +775,7 @@ class EfficientNet(nn.Module):
         self._dropout_p = gp.dropout_rate if gp.include_top else 0.0
         self.out_dim = head_out
         self.fp8 = False
+        self._frozen_bn = False
         self.rng = _Seeds()
         self.register_buffer("_ones_b", torch.ones(1), persistent=False)
         self._bn_layers = [m for m in self.modules() if isinstance(m, _BN)]
@@ -771,10 +823,38 @@ class EfficientNet(nn.Module):
         """BASELINE config #5: forward of the late-stage 1x1 convolutions (expand / project / head on the tiled MFMA path)
         with per-tensor-scaled OCP e4m3 activations and weights on gfx950's fp8 MFMA [ref: efficientnet_custom.py:104,
         122,283 are the convolutions concerned]; statistics, depthwise stages and the whole backward stay bf16 / fp32."""
+        if on and self._frozen_bn:
+            raise NotImplementedError("set_fp8 with frozen BatchNorm statistics (freeze_bn) is not implemented")
         self.fp8 = bool(on)
         for blk in self._blocks:
             blk.fp8 = bool(on)
         return self
+
+    def freeze_bn(self, on: bool = True):
+        """Frozen BatchNorm: every BatchNorm site of the encoder normalises with its RUNNING statistics, in ``train()`` mode too,
+        and leaves ``running_mean`` / ``running_var`` / ``num_batches_tracked`` untouched; the backward is torch's for a
+        BatchNorm in eval mode (dx = gamma*rsqrt(running_var + eps)*dz, dgamma = sum dz*xhat, dbeta = sum dz).  A site uses batch
+        statistics iff ``self.training and not self.frozen_bn``: ``eval()`` alone gives the same arithmetic (forward and, with
+        autograd on, backward), ``freeze_bn()`` + ``train()`` keeps drop-connect and dropout live -- the usual way to fine-tune or
+        continue pre-training at a small per-GPU batch; a micro-batched step and a full-batch step are then the same function of
+        the weights.  The flag survives ``train()`` / ``eval()``, is not part of ``state_dict()`` and covers the whole encoder:
+        the per-layer ``.training`` flags of the ``_bn*`` submodules are NOT consulted (as before).  Not implemented together
+        with ``set_fp8``.  Returns self."""
+        if on and self.fp8:
+            raise NotImplementedError("freeze_bn with the fp8 forward (set_fp8) is not implemented")
+        self._frozen_bn = bool(on)
+        for blk in self._blocks:
+            blk.frozen_bn = bool(on)
+        return self
+
+    @property
+    def frozen_bn(self) -> bool:
+        return self._frozen_bn
+
+    @property
+    def batch_stats(self) -> bool:
+        """do the BatchNorm sites use (and update from) batch statistics?  (``training and not frozen_bn``)"""
+        return self.training and not self._frozen_bn
 
     def set_recompute(self, mode: int = 0):
         """Activation memory of a kept autograd graph against backward work (the micro-batched contrastive step keeps as
@@ -844,7 +924,7 @@ class EfficientNet(nn.Module):
         self._last_seed = seed
         # num_batches_tracked of the ~120 BatchNorm layers: collected during the forward, incremented by one
         # multi-tensor launch at its end (116 one-element add launches per forward otherwise)
-        counters = [] if self.training else None
+        counters = [] if self.batch_stats else None
         bns = self._bn_layers if counters is not None else ()
         for bn in bns:
             bn.defer_count = counters
@@ -887,7 +967,7 @@ class EfficientNet(nn.Module):
         counters are left to ``side_call_end`` (after the join, on the main stream)"""
         global _BN_DEFER
         self._hold_counters = True
-        if self.training:
+        if self.batch_stats:
             _BN_DEFER = _BNDefer(self)
 
     def side_call_end(self):
@@ -923,9 +1003,9 @@ class EfficientNet(nn.Module):
             if torch.is_tensor(t_) and t_.is_cuda:
                 t_.record_stream(side)          # allocated on the main stream, read by the side chain (allocator reuse)
         seeds = [self.rng.next(), self.rng.next()]
-        training = self.training
-        counters = [[], []] if training else [None, None]
-        bns = self._bn_layers if training else ()
+        training, bstat = self.training, self.batch_stats      # (stochastic pieces / BatchNorm on batch statistics)
+        counters = [[], []] if bstat else [None, None]
+        bns = self._bn_layers if bstat else ()
         defer = None
 
         def chain(i):
@@ -939,7 +1019,7 @@ class EfficientNet(nn.Module):
         ys, scales, links = [None, None], [None, None], [None, None]
         try:
             torch.cuda.set_stream(side)
-            defer = _BNDefer(self) if training else None          # (zero-filled scratch: allocated and cleared on the side stream)
+            defer = _BNDefer(self) if bstat else None          # (zero-filled scratch: allocated and cleared on the side stream)
             for i in (0, 1):
                 chain(i)
                 ys[i], links[i], (n, h, w) = self._stem(xs[i])

@@ -116,6 +116,19 @@ __global__ void bn_eval_coeffs_k(const float* gamma, const float* beta, const fl
     shift[i] = beta[i] - rm[i] * sc;
 }
 
+// all four BNStats rows from the running statistics (a backward through a frozen BatchNorm needs xhat): scale / shift by the
+// very expressions of bn_eval_coeffs_k -- the eval forward keeps its bits
+__global__ void bn_eval_stats_k(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int c,
+                                float* mean, float* invstd, float* scale, float* shift) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c) return;
+    float sc = gamma[i] / sqrtf(rv[i] + eps);
+    scale[i] = sc;
+    shift[i] = beta[i] - rm[i] * sc;
+    mean[i] = rm[i];
+    invstd[i] = 1.f / sqrtf(rv[i] + eps);
+}
+
 __global__ __launch_bounds__(256) void bnact_apply_k(const mc_bnact_args p) {
     const int cvn = p.c / 8;
     const long long total = p.n_img * p.hw * cvn;
@@ -358,8 +371,12 @@ __global__ void bn_partials_from_se_sums_k(const float* __restrict__ sums, const
 // ACT: SiLU in front of the BatchNorm output (p.act == 1); MA: per-(image, channel) factor / addend on the upstream gradient
 // (p.mul / p.add).  Compile-time so that the plain form (BatchNorm2 of the projection: no activation, no factors) carries
 // 24 instead of 56 parameter registers and keeps four rows in flight in the reduce pass too.
-template <bool APPLY, bool ACT, bool MA>
+// FROZEN (reduce pass only): BatchNorm on running statistics -- dx = scale*dz does not depend on the reduction, so the pass
+// that leaves the (sum dz, sum dz*xhat) partials (xhat from the running statistics in p.mean / p.invstd) stores dx as well:
+// ONE pass over (x, g) instead of reduce + apply.  Own instantiations: the training-mode ones are compiled as before.
+template <bool APPLY, bool ACT, bool MA, bool FROZEN = false>
 __global__ __launch_bounds__(256) void bnact_bwd_k(const mc_bnact_args p) {
+    static_assert(!(APPLY && FROZEN), "the frozen form is the reduce pass with a store");
     RowMap rm(p.c);
     __shared__ float red[APPLY ? 1 : 256 * 16];
     const long long img = blockIdx.y;
@@ -378,7 +395,8 @@ __global__ __launch_bounds__(256) void bnact_bwd_k(const mc_bnact_args p) {
         for (int q = 0; q < 8; ++q) { a0[q] = 0.f; a1[q] = 0.f; }
         if (active) {
             float s[8], t[8], k0[8], k1[8], k2[8], mulv[8], addv[8];
-            if (ACT) { load8f(p.scale + v * 8, s); load8f(p.shift + v * 8, t); }
+            if (ACT || FROZEN) load8f(p.scale + v * 8, s);
+            if (ACT) load8f(p.shift + v * 8, t);
             if (APPLY) { load8f(p.coef + v * 8, k0); load8f(p.coef + p.c + v * 8, k1); load8f(p.coef + 2 * p.c + v * 8, k2); }
             else { load8f(p.mean + v * 8, k0); load8f(p.invstd + v * 8, k1); }
 #pragma unroll
@@ -413,7 +431,11 @@ __global__ __launch_bounds__(256) void bnact_bwd_k(const mc_bnact_args p) {
                 } else {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) { a0[q] += dz[q]; a1[q] += dz[q] * (x[q] - k0[q]) * k1[q]; }
-                    if (dxb) nt_store16(dxb + r * p.c + v * 8, pack8(dz));
+                    if constexpr (FROZEN) {
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) dz[q] *= s[q];
+                        nt_store16(dxb + r * p.c + v * 8, pack8(dz));
+                    } else if (dxb) nt_store16(dxb + r * p.c + v * 8, pack8(dz));
                 }
             };
             const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
@@ -475,6 +497,10 @@ __global__ __launch_bounds__(256) void bnact_bwd_k(const mc_bnact_args p) {
     }
 }
 
+// FROZEN (BatchNorm on running statistics): the same fp64 reduction of the same partials, but the mean terms of the
+// training-mode backward do not exist -- dx = scale*dz: gamma then holds SCALE (mean / invstd / count are not read) and the
+// coefficient block every apply-type consumer reads is exactly (scale, 0, 0)
+template <bool FROZEN>
 __global__ void bn_bwd_finalize_k(const float* __restrict__ partials, int rows, int c, double count,
                                   const float* __restrict__ gamma, const float* __restrict__ mean,
                                   const float* __restrict__ invstd, float* __restrict__ dgamma,
@@ -507,10 +533,30 @@ __global__ void bn_bwd_finalize_k(const float* __restrict__ partials, int rows, 
     for (int r = 0; r < 16; ++r) { s0 += sh[0][r][cl]; s1 += sh[1][r][cl]; }
     dbeta[i] = (float)s0;
     dgamma[i] = (float)s1;
+    if (FROZEN) {
+        coef[i] = gamma[i];
+        coef[c + i] = 0.f;
+        coef[2 * c + i] = 0.f;
+        return;
+    }
     double gi = (double)gamma[i] * (double)invstd[i];
     coef[i] = (float)gi;
     coef[c + i] = (float)(-gi * (double)invstd[i] * s1 / count);
     coef[2 * c + i] = (float)(gi * ((double)invstd[i] * s1 * (double)mean[i] - s0) / count);
+}
+
+// frozen BatchNorm0 in front of a 1x1 conv e = x W^T (W [n, k] fp32): de = diag(scale) dz, so dx = dz (diag(scale) W) and
+// dW = diag(scale) (dz^T x) -- w_t [k, n] = 16-bit((scale.W)^T), the data-gradient GEMM's operand, and / or the row scale of an
+// fp32 [n, k] matrix (out may alias src)
+__global__ void bn_frozen_rows_k(const float* src, const float* __restrict__ scale, int n, int k,
+                                 bf16_t* __restrict__ w_t, float* out) {
+    const long long total = (long long)n * k;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int i = (int)(idx / k), j = (int)(idx % k);
+        const float v = src[idx] * scale[i];
+        if (w_t) w_t[(long long)j * n + i] = f2bf(v);
+        if (out) out[idx] = v;
+    }
 }
 
 // ---------------------------------------------------------------- squeeze-excite MLP
@@ -663,6 +709,14 @@ extern "C" int mc_bn_eval_coeffs(const float* gamma, const float* beta, const fl
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
+extern "C" int mc_bn_eval_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                float eps, int c, float* mean, float* invstd, float* scale, float* shift, void* stream) {
+    MC_CHECK(gamma && beta && running_mean && running_var && mean && invstd && scale && shift && c > 0, "bn_eval_stats: bad args");
+    hipLaunchKernelGGL(bn_eval_stats_k, dim3(mc_div_up(c, 128)), dim3(128), 0, (hipStream_t)stream, gamma, beta,
+                       running_mean, running_var, eps, c, mean, invstd, scale, shift);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
 static int bwd_grid_x(const mc_bnact_args& p) {
     int cv = p.c / 8;
     int cvp = rowmap_width(cv, 0, false);
@@ -790,6 +844,21 @@ extern "C" int mc_bnact_bwd_reduce(const mc_bnact_args* a, void* stream) {
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
+extern "C" int mc_bnact_bwd_frozen(const mc_bnact_args* a, void* stream) {
+    const mc_bnact_args& p = *a;
+    if (int e = check_bnact(p)) return e;
+    MC_CHECK(p.partials && p.mean && p.invstd && p.dx, "bnact_bwd_frozen: null partials/mean/invstd/dx");
+    MC_CHECK(mc_aligned16(p.dx) && (!p.g || mc_aligned16(p.g)), "bnact_bwd_frozen: g / dx must be 16-byte aligned");
+    const dim3 grid(bwd_grid_x(p), (unsigned)p.n_img), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const bool act = p.act == 1, ma = p.mul || p.add;
+    if (act && ma) hipLaunchKernelGGL((bnact_bwd_k<false, true, true, true>), grid, block, 0, st, p);
+    else if (act) hipLaunchKernelGGL((bnact_bwd_k<false, true, false, true>), grid, block, 0, st, p);
+    else if (ma) hipLaunchKernelGGL((bnact_bwd_k<false, false, true, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((bnact_bwd_k<false, false, false, true>), grid, block, 0, st, p);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
 extern "C" int mc_bnact_bwd_apply(const mc_bnact_args* a, void* stream) {
     const mc_bnact_args& p = *a;
     if (int e = check_bnact(p)) return e;
@@ -802,8 +871,24 @@ extern "C" int mc_bn_bwd_finalize(const float* partials, int rows, int c, double
                                   const float* mean, const float* invstd, float* dgamma, float* dbeta, float* coef,
                                   void* stream) {
     MC_CHECK(partials && gamma && mean && invstd && dgamma && dbeta && coef && rows > 0 && c > 0, "bn_bwd_finalize: bad args");
-    hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(mc_div_up(c, 16)), dim3(256), 0, (hipStream_t)stream, partials, rows, c,
+    hipLaunchKernelGGL(bn_bwd_finalize_k<false>, dim3(mc_div_up(c, 16)), dim3(256), 0, (hipStream_t)stream, partials, rows, c,
                        count, gamma, mean, invstd, dgamma, dbeta, coef);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_bn_bwd_finalize_frozen(const float* partials, int rows, int c, const float* scale, float* dgamma,
+                                         float* dbeta, float* coef, void* stream) {
+    MC_CHECK(partials && scale && dgamma && dbeta && coef && rows > 0 && c > 0, "bn_bwd_finalize_frozen: bad args");
+    hipLaunchKernelGGL(bn_bwd_finalize_k<true>, dim3(mc_div_up(c, 16)), dim3(256), 0, (hipStream_t)stream, partials, rows, c,
+                       0.0, scale, (const float*)nullptr, (const float*)nullptr, dgamma, dbeta, coef);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_bn_frozen_rows(const float* src, const float* scale, int n, int k, mc_bf16* w_t, float* out, void* stream) {
+    MC_CHECK(src && scale && (w_t || out) && n > 0 && k > 0, "bn_frozen_rows: bad args");
+    const long long total = (long long)n * k;
+    hipLaunchKernelGGL(bn_frozen_rows_k, dim3((unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048)), dim3(256), 0,
+                       (hipStream_t)stream, src, scale, n, k, (bf16_t*)w_t, out);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

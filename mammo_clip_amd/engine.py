@@ -448,9 +448,15 @@ def _step_micro(self, batch: Dict, k: int) -> Dict[str, torch.Tensor]:
     # launch (recompute mode 1 on those blocks: the expanded tensor is rebuilt by one GEMM in the backward), so all micro-batches
     # of a step see one arithmetic and a re-forward reproduces its first forward bit for bit
     xdw_modes = enc_.xdw_reforward_modes() if hasattr(enc_, "xdw_reforward_modes") else []
+    # frozen BatchNorm statistics (EfficientNet.freeze_bn): the k micro-batches are the same function of the weights as one pass
+    # over the whole batch; choosing the GEMM kernel family by the whole batch's rows makes them the same roundings as well
+    # (ops.set_rows_select_scale).  With batch statistics the two differ anyway and nothing changes
+    rows_x = ops.set_rows_select_scale(k) if getattr(enc_, "frozen_bn", False) else None
     try:
         return self._step_micro_body(batch, k)
     finally:
+        if rows_x is not None:
+            ops.set_rows_select_scale(rows_x)
         for blk, mode_ in xdw_modes:
             blk.recompute = mode_
 

@@ -159,16 +159,20 @@ _SIGS = {
     "mc_bn_gram_partials": ([P, I, P, P, D, I, I, P, P], I),
     "mc_bn_finalize": ([P, I, I, D, P, P, P, P, F, F, I, P, P, P, P, P], I),
     "mc_bn_eval_coeffs": ([P, P, P, P, F, I, P, P, P], I),
+    "mc_bn_eval_stats": ([P, P, P, P, F, I, P, P, P, P, P], I),
     "mc_bnact_rows": ([C.POINTER(BnactArgs)], I),
     "mc_bnact_img_splits": ([C.POINTER(BnactArgs)], I),
     "mc_bnact_apply": ([C.POINTER(BnactArgs), P], I),
     "mc_bnact_pool": ([C.POINTER(BnactArgs), P], I),
     "mc_bnact_bwd_reduce": ([C.POINTER(BnactArgs), P], I),
     "mc_bnact_bwd_apply": ([C.POINTER(BnactArgs), P], I),
+    "mc_bnact_bwd_frozen": ([C.POINTER(BnactArgs), P], I),
     "mc_bnact_se_dgate": ([C.POINTER(BnactArgs), P], I),
     "mc_bnact_se_sums": ([C.POINTER(BnactArgs), P], I),
     "mc_bn_partials_from_se_sums": ([P, P, P, F, LL, I, P, P], I),
     "mc_bn_bwd_finalize": ([P, I, I, D, P, P, P, P, P, P, P], I),
+    "mc_bn_bwd_finalize_frozen": ([P, I, I, P, P, P, P, P], I),
+    "mc_bn_frozen_rows": ([P, P, I, I, P, P, P], I),
     "mc_colsum_rows": ([LL, I], I),
     "mc_colsum_bf16": ([P, LL, I, LL, P, P, I, P], I),
     "mc_se_fwd": ([P, P, P, P, P, I, I, I, P, P, P], I),

@@ -233,6 +233,23 @@ def linear_fwd_fp8(x, w, amax_x=None, amax_w=None, stats=False, batch_w=None):
 
 
 ROWS_MIN_M = 8192       # below this the tiled kernel is as good
+# The row count the threshold is compared with is M * _ROWS_SELECT_X.  1 everywhere, except in a micro-batched step on frozen
+# BatchNorm statistics (engine._step_micro): there the k micro-batches are the same function of the weights as one pass over the
+# whole per-GPU batch, and with the kernel family chosen by the WHOLE batch's rows (k * M) they are the same roundings too -- the
+# row-streaming and the tile kernels sum in different orders before their 16-bit store.  The row-streaming kernels take any M.  Other row-count-dependent choices (epilogue support, depthwise
+# predicates, grid splits) stay per call; the speed of the row-streaming kernels below ROWS_MIN_M rows is not measured.
+_ROWS_SELECT_X = 1
+
+
+def set_rows_select_scale(times):
+    """choose between the row-streaming and the tile kernels as a call with `times` x the rows would; returns the previous factor"""
+    global _ROWS_SELECT_X
+    prev, _ROWS_SELECT_X = _ROWS_SELECT_X, max(1, int(times))
+    return prev
+
+
+def _rows_streamed(M):
+    return M * _ROWS_SELECT_X >= ROWS_MIN_M
 
 
 def gemm_rows(x, w, y, residual=None, pro=None, stats=False, kind=None, bias=None):
@@ -267,7 +284,7 @@ def proj_dgrad_fusable(M, n_out, k_in, rows_per_img):
     if n_out < PROJ_DGRAD_FUSE_MIN_N:
         return False
     lib_ = L.load()
-    return (M >= ROWS_MIN_M and n_out <= 256 and k_in <= 128 and rows_per_img % 16 == 0 and rows_per_img >= 16
+    return (_rows_streamed(M) and n_out <= 256 and k_in <= 128 and rows_per_img % 16 == 0 and rows_per_img >= 16
             and bool(lib_.mc_gemm_rows_supported(n_out, k_in)) and not _prefer_tiles(n_out, k_in)
             and bool(lib_.mc_gemm_rows_epi_supported(M, n_out, k_in, rows_per_img, 1))
             and bool(lib_.mc_gemm_rows_epi_supported(M, n_out, k_in, rows_per_img, 2)))
@@ -310,7 +327,7 @@ def proj_dgrad_bn_apply(dp, w_t, d, stats, coef, mul, add, add_scale, rows_per_i
 
 
 def _rows_ok(M, N, K, bias, act):
-    return act == 0 and M >= ROWS_MIN_M and L.load().mc_gemm_rows_supported(N, K)
+    return act == 0 and _rows_streamed(M) and L.load().mc_gemm_rows_supported(N, K)
 
 
 def _prefer_tiles(N, K):
@@ -474,7 +491,7 @@ def _linear_wgrad_impl(dy, x, pro=None, out=None, tag=""):
     M, N = dy.shape
     K = x.shape[1]
     dw = out if out is not None else empty((N, K), torch.float32, dy)
-    if M >= ROWS_MIN_M and L.load().mc_wgrad_rows_supported(N, K) and (pro is None or pro[0] is not None):
+    if _rows_streamed(M) and L.load().mc_wgrad_rows_supported(N, K) and (pro is None or pro[0] is not None):
         a = L.WgradRowsArgs()
         a.dY, a.N, a.lddy = _p(dy), N, dy.stride(0)
         a.X, a.K, a.ldx, a.M = _p(x), K, x.stride(0), M
@@ -518,7 +535,7 @@ _XBWD_OK = {}
 
 def xbwd_rows_ok(M, n_out, k_in):
     """does ONE launch give both gradients of the 1x1 conv [M, k_in] -> [M, n_out] (mc_xbwd_rows_bf16)?"""
-    if not FUSE_XBWD or M < ROWS_MIN_M:
+    if not FUSE_XBWD or not _rows_streamed(M):
         return False
     hit = _XBWD_OK.get((n_out, k_in))
     if hit is None:
@@ -893,11 +910,15 @@ def bn_finalize(partials, count, gamma, beta, running_mean, running_var, momentu
 
 
 def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps):
+    """BNStats of a BatchNorm on its running statistics (eval mode / EfficientNet.freeze_bn): scale and shift for the forward,
+    mean = running_mean and invstd = rsqrt(running_var + eps) for a backward (the xhat of bnact_bwd(frozen=True), the
+    squeeze-excite sums and the depthwise data-gradient epilogues); count 0.0: no batch was reduced."""
     c = gamma.shape[0]
     buf = empty((4, c), torch.float32, gamma)
-    L.call("mc_bn_eval_coeffs", _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, c, _p(buf[2]), _p(buf[3]), _st())
+    L.call("mc_bn_eval_stats", _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, c, _p(buf[0]), _p(buf[1]), _p(buf[2]),
+           _p(buf[3]), _st())
     s = BNStats()
-    s.mean, s.invstd, s.scale, s.shift, s.count = None, None, buf[2], buf[3], 0.0
+    s.mean, s.invstd, s.scale, s.shift, s.count = buf[0], buf[1], buf[2], buf[3], 0.0
     return s
 
 
@@ -971,13 +992,32 @@ def bn_partials_from_se_sums(sums, gate, dpooled, add_scale):
 
 
 def bnact_bwd(x, n_img, hw, c, stats, gamma, act, g=None, mul=None, add=None, rowscale=None, add_scale=1.0,
-              partials=None):
+              partials=None, frozen=False):
     """Backward through y = act(BN_train(x)) (* rowscale).  Returns (dx bf16, dgamma, dbeta).
-    partials: precomputed [rows, 2, c] reduction (skips the reduce pass over the big tensors)."""
+    partials: precomputed [rows, 2, c] reduction (skips the reduce pass over the big tensors).
+    frozen: BatchNorm on running statistics (stats from bn_eval_coeffs): dx = scale*dz needs no reduction, so ONE pass over
+    (x, g) stores it and leaves the dgamma / dbeta partials (mc_bnact_bwd_frozen); with partials given, the apply pass alone
+    runs, on the coefficients (scale, 0, 0)."""
     a = _bnact(x, n_img, hw, c, stats.scale, stats.shift, act)
     a.g, a.mul, a.add, a.rowscale = _p(g), _p(mul), _p(add), _p(rowscale)
     a.add_scale = add_scale
     a.mean, a.invstd = _p(stats.mean), _p(stats.invstd)
+    if frozen:
+        dx = empty((n_img * hw, c), BF16, x)
+        a.dx = _p(dx)
+        if partials is None:
+            rows = L.load().mc_bnact_rows(C.byref(a))
+            partials = empty((rows, 2, c), torch.float32, x)
+            a.partials = _p(partials)
+            _note(2 * n_img * hw * c * (3 if g is not None else 2))
+            L.call("mc_bnact_bwd_frozen", C.byref(a), _st())
+            _, dgamma, dbeta = bn_bwd_coefs(partials, 0, stats, gamma, frozen=True)
+        else:
+            coef, dgamma, dbeta = bn_bwd_coefs(partials, 0, stats, gamma, frozen=True)
+            a.coef = _p(coef)
+            _note(2 * n_img * hw * c * (3 if g is not None else 2))
+            L.call("mc_bnact_bwd_apply", C.byref(a), _st())
+        return dx, dgamma, dbeta
     if partials is not None:
         part, rows = partials, partials.shape[0]
     else:
@@ -1015,15 +1055,37 @@ def bnact_bwd_reduce_dz(x, n_img, hw, c, stats, act, g):
     return dz, part
 
 
-def bn_bwd_coefs(partials, count, stats, gamma):
+def bn_bwd_coefs(partials, count, stats, gamma, frozen=False):
     """Finalize a BatchNorm-backward reduction: partials [rows, 2, c] = (sum dz, sum dz*xhat) -> (coef [3, c], dgamma,
-    dbeta) with dx = coef[0]*dz + coef[1]*x + coef[2] (the apply pass, or the folded GEMM operands of bn_fold_*)."""
+    dbeta) with dx = coef[0]*dz + coef[1]*x + coef[2] (the apply pass, or the folded GEMM operands of bn_fold_*).
+    frozen (running statistics): the same reduction, coef = (scale, 0, 0) exactly; count is not used."""
     c = partials.shape[-1]
     dgamma, dbeta = empty((c,), torch.float32, partials), empty((c,), torch.float32, partials)
     coef = empty((3, c), torch.float32, partials)
+    if frozen:
+        L.call("mc_bn_bwd_finalize_frozen", _p(partials), partials.shape[0], c, _p(stats.scale), _p(dgamma), _p(dbeta), _p(coef), _st())
+        return coef, dgamma, dbeta
     L.call("mc_bn_bwd_finalize", _p(partials), partials.shape[0], c, float(count), _p(gamma), _p(stats.mean),
            _p(stats.invstd), _p(dgamma), _p(dbeta), _p(coef), _st())
     return coef, dgamma, dbeta
+
+
+def bn_frozen_weight_t(w_f32, scale):
+    """[k, n] 16-bit image of (diag(scale) W)^T for W [n, k] fp32: the data-gradient operand of a 1x1 conv behind a frozen
+    BatchNorm, dx = dz (diag(scale) W) (not cached: scale is a per-call tensor)"""
+    n, k = w_f32.shape
+    assert w_f32.is_contiguous()
+    w_t = empty((k, n), BF16, w_f32)
+    L.call("mc_bn_frozen_rows", _p(w_f32), _p(scale), n, k, _p(w_t), None, _st())
+    return w_t
+
+
+def rowscale_f32_(m, scale):
+    """m [n, k] fp32 <- diag(scale) m, in place: the weight gradient diag(scale) (dz^T x) of a 1x1 conv behind a frozen BatchNorm"""
+    n, k = m.shape
+    assert m.is_contiguous() and m.dtype == torch.float32
+    L.call("mc_bn_frozen_rows", _p(m), _p(scale), n, k, None, _p(m), _st())
+    return m
 
 
 def bn_fold_expand_bwd(dz, x, we_f32, we_bf16, coef, dbeta, rows, residual=None, gram=None):
