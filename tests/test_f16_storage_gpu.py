@@ -39,6 +39,14 @@ def test_f16_build_every_kernel_test():
     assert " passed" in p.stdout and "failed" not in p.stdout, p.stdout[-1000:]
 
 
+def test_f16_build_exact_gemm_tests():
+    """tests/test_gemm_exact_gpu.py -- the GEMM kernels on +-1 operands, exact against fp64 -- on the f16 build (the same draw
+    is exact there: |y| <= 512 needs 10 of f16's 11 significand bits)"""
+    p = _run(["-m", "pytest", os.path.join(HERE, "test_gemm_exact_gpu.py"), "-m", "gpu", "-x", "-q"], 600)
+    assert p.returncode == 0, p.stdout[-3000:]
+    assert " passed" in p.stdout and "failed" not in p.stdout and "skipped" not in p.stdout, p.stdout[-1000:]
+
+
 def test_f16_model_kats_and_config1_vs_reference():
     """the reference-generated fixtures of the model level on the f16 build: MBConv / BERT / loss known-answer tests, the
     config-#1 end-to-end fixtures (eval |loss - reference| <= 1e-3 on three seeds; train mode, gradients)"""

@@ -3,7 +3,10 @@ same op, on seeded inputs.  GPU only (`pytest -m gpu`).
 
 Tolerances: kernels compute in fp32 from bf16 operands and round the result once to bf16, so the bound is
 bf16 round-off: max-abs error <= 1e-2 * max|ref| (2^-8 = 3.9e-3 per rounding) unless noted; fp32-in/fp32-out
-kernels are held to 1e-4.
+kernels are held to 1e-4.  For the GEMM kernels that bound is global: an error confined to one output tile -- one lost
+reduction element, a K tail one chunk short, an unwritten last row of a ragged tile, a write outside the tile -- stays under
+1e-2 * max|ref| of a Gaussian product.  tests/test_gemm_exact_gpu.py runs the same kernels on +-1 operands, where the product
+is exact and compared with torch.equal, inside guarded buffers, at the smallest shapes that reach each path.
 
 Launchers with a capped grid (the row, element, cast and column-sum kernels) run their later passes only past a
 row / element count; the `*_past_the_grid_cap` tests cross each cap by one ragged workgroup, with fp64 references:
