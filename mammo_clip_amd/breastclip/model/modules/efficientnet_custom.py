@@ -124,19 +124,6 @@ class StatTape:
         return v
 
 
-_TAPE = None
-
-
-def set_stat_tape(tape):
-    """install (or remove: None) the tape the next encoder forwards record on / replay from (engine._step_micro)"""
-    global _TAPE
-    _TAPE = tape
-
-
-def _replaying():
-    return _TAPE is not None and _TAPE.mode == "replay"
-
-
 class _BNDefer:
     """Running-statistic updates of an encoder call that runs on a SIDE stream beside another call of the same encoder
     (model/clip.py: the second image view).  Both calls update the same buffers -- r <- (1 - m) r + m s, view 1 first
@@ -173,33 +160,52 @@ class _BNDefer:
         self.used = []
 
 
-_BN_DEFER = None
+class _Call:
+    """Everything ONE chain of one encoder forward knows beyond its tensors; made by ``EfficientNet._new_call`` and handed
+    to the stem, every block and the head like ``link`` is.  Nothing of it outlives the call, so an exception leaves nothing behind.
+      tape            the StatTape this forward records on / replays from, or None (both chains of forward_pair share one)
+      update_running  do the finalize launches update the running statistics (and the batch counters)?
+      defer           the _BNDefer whose scratch slices take those updates instead of the buffers (side chain), or None
+      counters        collects the num_batches_tracked tensors: the encoder bumps them with ONE launch when the call ends
+                      (None -- a block called on its own -- bumps each at once)
+      seed            of the call's drop-connect / dropout masks
+      head            (e, st, n, h, w, cout) of the head conv, left by _HeadFn for the feature-map forms of forward"""
+    __slots__ = ("tape", "update_running", "defer", "counters", "seed", "head")
+
+    def __init__(self, tape=None, update_running=True, defer=None, counters=None, seed=None):
+        self.tape, self.update_running, self.defer, self.counters, self.seed, self.head = tape, update_running, defer, counters, seed, None
+
+    @property
+    def replaying(self):
+        return self.tape is not None and self.tape.mode == "replay"
+
+    def taped(self, active, fn):
+        """fn() -- or, at a site whose values travel on the tape (``active``), its recorded value in a replay; recorded otherwise"""
+        if not active or self.tape is None:
+            return fn()
+        return self.tape.get() if self.tape.mode == "replay" else self.tape.put(fn())
 
 
-def _bn_stats(partials, count, bn: nn.BatchNorm2d, training: bool):
-    if training:
-        if _replaying():
-            return _TAPE.get()
-        if _BN_DEFER is not None and bn.track_update:
-            rm, rv = _BN_DEFER.scratch(bn)
-        else:
-            rm, rv = bn.running_mean, bn.running_var
-        st = ops.bn_finalize(partials, count, bn.weight, bn.bias, rm, rv, BN_MOMENTUM, BN_EPS, bn.track_update)
-        if bn.track_update:
-            if bn.defer_count is not None:
-                bn.defer_count.append(bn.num_batches_tracked)     # the encoder bumps all counters with ONE launch
-            else:
-                bn.num_batches_tracked += 1
-        if _TAPE is not None:
-            _TAPE.put(st)
+def _bn_stats(call, partials, count, bn: nn.BatchNorm2d, training: bool):
+    if not training:
+        return ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS)
+
+    def finalize():
+        upd = call.update_running
+        rm, rv = call.defer.scratch(bn) if upd and call.defer is not None else (bn.running_mean, bn.running_var)
+        st = ops.bn_finalize(partials, count, bn.weight, bn.bias, rm, rv, BN_MOMENTUM, BN_EPS, upd)
+        if upd and call.counters is not None:
+            call.counters.append(bn.num_batches_tracked)
+        elif upd:
+            bn.num_batches_tracked += 1
         return st
-    return ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, BN_EPS)
+    return call.taped(True, finalize)
 
 
-def _conv_stats(fn, training, *a, stats=True, **kw):
+def _conv_stats(call, fn, training, *a, stats=True, **kw):
     """run a producer that can leave BatchNorm statistics partials (stats=True -> (y, partials)); a replaying tape needs none,
-    nor does a backward that rebuilds y (stats=False)"""
-    if not stats or (training and _replaying()):
+    nor does a backward that rebuilds y (stats=False, no call)"""
+    if not stats or (training and call.replaying):
         return fn(*a, **kw), None
     return fn(*a, stats=True, **kw)
 
@@ -229,8 +235,9 @@ class _StemFn(torch.autograd.Function):
     """_conv_stem (3x3 s2, static pad) + _bn0 + swish [ref: efficientnet_custom.py:273]."""
 
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, mod, link=None):
-        """link (round 5): a ``_StemLink`` -- the stem then returns its RAW conv output e and block 0 (no expand conv: its
+    def forward(ctx, x, w, gamma, beta, mod, link=None, call=None):
+        """call: the ``_Call`` of the encoder forward this is part of (None: the stem on its own).
+        link (round 5): a ``_StemLink`` -- the stem then returns its RAW conv output e and block 0 (no expand conv: its
         depthwise stage reads the stem's output directly) applies bn0 + swish while it stages its LDS tiles, exactly like every
         other block does with its own expand conv; the activated 48-channel 760x456 tensor (the widest map of the network) is
         never written or read.  The backward mirrors it: block 0's depthwise data gradient finishes the bn0 + swish backward in
@@ -241,9 +248,9 @@ class _StemFn(torch.autograd.Function):
         c0 = w.shape[0]
         patches = ops.stem_im2col(x, l, t, oh, ow)
         wb = ops.stem_weight_prep(w)
-        training = mod.batch_stats
-        e, part = _conv_stats(ops.linear_fwd, training, patches, wb)
-        st = _bn_stats(part, n * oh * ow, mod._bn0, training)
+        training, call = mod.batch_stats, call if call is not None else _Call()
+        e, part = _conv_stats(call, ops.linear_fwd, training, patches, wb)
+        st = _bn_stats(call, part, n * oh * ow, mod._bn0, training)
         ctx.mod, ctx.st, ctx.geo, ctx.frozen = mod, st, (n, h, wd, oh, ow, c0), not training
         ctx.raw = (x.mean, x.std) if isinstance(x, ops.RawImages) else None
         ctx.save_for_backward(x.data if ctx.raw else x, e)
@@ -283,7 +290,7 @@ class _StemFn(torch.autograd.Function):
             dw = ops.rowscale_f32_(dw, ctx.st.scale)
         gw, gg, gb = ops.deliver_param_grads((mod._conv_stem.weight, mod._bn0.weight, mod._bn0.bias),
                                              (dw[:, :27].reshape(c0, 3, 3, 3), dgamma, dbeta))
-        return (None, gw, gg, gb, None) + ((None,) if link is not None else ())
+        return None, gw, gg, gb, None, None, None        # (autograd drops the Nones of trailing arguments that were not passed)
 
 
 class _StemLink:
@@ -295,26 +302,26 @@ class _StemLink:
         self.st, self.part = None, None
 
 
-def _expand_conv(pl, x, we, stats=True):
+def _expand_conv(call, pl, x, we, stats=True):
     """_expand_conv of one block: (e [rows, cexp] bf16, BatchNorm0 column-statistic partials) (deterministic: the backward's
-    rebuild, stats=False, reproduces the forward's tensor bit for bit)."""
+    rebuild, stats=False and no call, reproduces the forward's tensor bit for bit)."""
     if pl.fp8_expand:
         # config #5: fp8 (e4m3, per-tensor scale) activations and weights on the fp8 MFMA; BatchNorm statistics
         # and everything downstream stay on the bf16 / fp32 path; backward uses the bf16 tensors (straight-through)
         return ops.linear_fwd_fp8(x, we, stats=True)
-    return _conv_stats(ops.linear_fwd, pl.batch_stats, x, we, stats=stats)
+    return _conv_stats(call, ops.linear_fwd, pl.batch_stats, x, we, stats=stats)
 
 
-def _depthwise(blk, pl, x, e, we, wkkc, pro0, stats=True):
+def _depthwise(call, blk, pl, x, e, we, wkkc, pro0, stats=True):
     """depthwise stage of one block: (d [n*oh*ow, cexp] bf16, BatchNorm1 partials) from the block input x (fused expand +
     depthwise launch: from the UNROUNDED expand output) or from e / the linked stem output x (pro0 = the BatchNorm0 + swish
     prologue).  The backward rebuilds d through this very function (stats=False): same launch, bit for bit."""
     if pl.xdw:
-        return _conv_stats(ops.mbconv_xdw_fwd, pl.batch_stats, x, we, pro0, wkkc, *pl.dw, stats=stats)
-    return _conv_stats(ops.dwconv_fwd, pl.batch_stats, e if blk.args.expand != 1 else x, wkkc, *pl.dw, stats=stats, pro=pro0)
+        return _conv_stats(call, ops.mbconv_xdw_fwd, pl.batch_stats, x, we, pro0, wkkc, *pl.dw, stats=stats)
+    return _conv_stats(call, ops.dwconv_fwd, pl.batch_stats, e if blk.args.expand != 1 else x, wkkc, *pl.dw, stats=stats, pro=pro0)
 
 
-def _project_conv(pl, d, act1, st1, gate, wp, stats=True):
+def _project_conv(call, pl, d, act1, st1, gate, wp, stats=True):
     """_project_conv of one block: (p [n*oh*ow, cout] bf16, BatchNorm2 partials)"""
     ohw = pl.oh * pl.ow
     if pl.fp8_project:
@@ -322,7 +329,7 @@ def _project_conv(pl, d, act1, st1, gate, wp, stats=True):
         return ops.linear_fwd_fp8(act1, wg, stats=True, batch_w=(pl.n, ohw))
     # stored activation: only the SE gate is applied; else BN1 + SiLU + gate while the GEMM stages its A operand
     src, pro = (act1, (None, None, gate, ohw)) if pl.keep_act else (d, (st1.scale, st1.shift, gate, ohw))
-    return _conv_stats(ops.linear_fwd, pl.batch_stats, src, wp, stats=stats, pro=pro)
+    return _conv_stats(call, ops.linear_fwd, pl.batch_stats, src, wp, stats=stats, pro=pro)
 
 
 class _MBConvFn(torch.autograd.Function):
@@ -330,7 +337,7 @@ class _MBConvFn(torch.autograd.Function):
     made once, by ``MBConvBlock.plan``, when the forward runs; the backward reads the plan stored with the graph."""
 
     @staticmethod
-    def forward(ctx, x, rowscale, blk, n, h, w, recording, link, *params):
+    def forward(ctx, x, rowscale, blk, n, h, w, recording, link, call, *params):
         a = blk.args
         pl = blk.plan(n, h, w, recording)
         # bstat: BatchNorm on batch statistics (statistics epilogues, finalize launches, their tape entries); training: the module's
@@ -345,43 +352,35 @@ class _MBConvFn(torch.autograd.Function):
                 # over x, 6 x narrower than e), from the statistics tape of a re-forward, or from the running statistics (eval).
                 # x^T x and colsum(x) of the Gram statistics pass are what the folded BatchNorm0 backward of this block needs
                 # again: they stay in the graph (a few KB) and travel on the statistics tape to the re-forward's backward
-                if bstat and _replaying():
-                    part0, gram = None, _TAPE.get()
-                elif bstat:
-                    part0, gram = ops.bn_gram_partials(x, we, n * h * w)
-                    if _TAPE is not None:
-                        _TAPE.put(gram)
-                else:
-                    part0 = None
+                part0 = None
+
+                def gram_pass():
+                    nonlocal part0
+                    part0, xtx = ops.bn_gram_partials(x, we, n * h * w)
+                    return xtx
+                gram = call.taped(True, gram_pass) if bstat else None
             else:
-                e, part0 = _expand_conv(pl, x, we)
-            st0 = _bn_stats(part0, n * h * w, blk._bn0, bstat)
+                e, part0 = _expand_conv(call, pl, x, we)
+            st0 = _bn_stats(call, part0, n * h * w, blk._bn0, bstat)
             pro0 = (st0.scale, st0.shift)
         else:
             # block 0 behind a linked stem: x is the stem's RAW conv output, its bn0 + swish is this block's prologue
             pro0 = (link.st.scale, link.st.shift) if link is not None else None
-        d, part1 = _depthwise(blk, pl, x, e, we, wkkc, pro0)
-        st1 = _bn_stats(part1, n * ohw, blk._bn1, bstat)
+        d, part1 = _depthwise(call, blk, pl, x, e, we, wkkc, pro0)
+        st1 = _bn_stats(call, part1, n * ohw, blk._bn1, bstat)
         # Late stages (project conv on the tiled GEMM): the squeeze pass also stores A = silu(bn1(d)); the project GEMM
         # and its weight gradient then apply only the SE gate instead of re-evaluating BN+SiLU per output tile.
+        # (that pass runs in a replay too: act1 is needed; in the early stages the squeeze pass only produces the taped means)
         if pl.keep_act:
             pooled, act1 = ops.bnact_pool(d, n, ohw, a.cexp, st1.scale, st1.shift, 1, keep_act=True)
-        elif training and _replaying():
-            pooled, act1 = _TAPE.get(), None                      # (early stages: the squeeze pass only produced this)
         else:
-            pooled, act1 = ops.bnact_pool(d, n, ohw, a.cexp, st1.scale, st1.shift, 1), None
-            if training and _TAPE is not None:
-                _TAPE.put(pooled)
-        if training and _replaying():
-            gate = _TAPE.get()                                     # (every block: the squeeze-excite MLP's two launches)
-        else:
-            gate = ops.se_fwd(pooled, blk._se_reduce.weight.view(a.cse, a.cexp), blk._se_reduce.bias,
-                              blk._se_expand.weight.view(a.cexp, a.cse), blk._se_expand.bias)
-            if training and _TAPE is not None:
-                _TAPE.put(gate)
+            pooled, act1 = call.taped(training, lambda: ops.bnact_pool(d, n, ohw, a.cexp, st1.scale, st1.shift, 1)), None
+        # (every block: a replay saves the squeeze-excite MLP's two launches)
+        gate = call.taped(training, lambda: ops.se_fwd(pooled, blk._se_reduce.weight.view(a.cse, a.cexp), blk._se_reduce.bias,
+                                                       blk._se_expand.weight.view(a.cexp, a.cse), blk._se_expand.bias))
         wp = blk.w_project()
-        p, part2 = _project_conv(pl, d, act1, st1, gate, wp)
-        st2 = _bn_stats(part2, n * ohw, blk._bn2, bstat)
+        p, part2 = _project_conv(call, pl, d, act1, st1, gate, wp)
+        st2 = _bn_stats(call, part2, n * ohw, blk._bn2, bstat)
         y = ops.bnact_apply(p, n, ohw, a.cout, st2.scale, st2.shift, 0,
                             rowscale=rowscale if a.skip else None, res=x if a.skip else None)
         # what the plan does not store (recompute modes, see EfficientNet.set_recompute) the backward rebuilds from the block
@@ -406,14 +405,20 @@ class _MBConvFn(torch.autograd.Function):
         frozen = not pl.batch_stats
         if frozen:
             _no_fp8_frozen(blk)
+
+        def expand_bwd(g, w_t):
+            """(dx, dWe) of the expand conv from the gradient g of its output; w_t: the [cin, cexp] weight image of the data gradient"""
+            if pl.xbwd:                                      # one pass over g for both gradients (round 5)
+                return ops.xbwd_rows(g, x, w_t, residual=dy if a.skip else None)
+            return ops.linear_dgrad(g, sv["we"], residual=dy if a.skip else None, w_t=w_t), ops.linear_wgrad(g, x)
         if a.expand != 1 and e is None and not (pl.efree or pl.efree_s2):     # (recompute modes: same kernels, statistics epilogues off)
-            e = _expand_conv(pl, x, sv["we"], stats=False)[0]
+            e = _expand_conv(None, pl, x, sv["we"], stats=False)[0]
         if d is None:
-            d = _depthwise(blk, pl, x, e, sv["we"], sv["wkkc"], pro0, stats=False)[0]
+            d = _depthwise(None, blk, pl, x, e, sv["we"], sv["wkkc"], pro0, stats=False)[0]
             if pl.keep_act:
                 act1 = ops.bnact_pool(d, n, ohw, a.cexp, st1.scale, st1.shift, 1, keep_act=True)[1]
         if p is None:                                        # mode 4: the projection conv again, from the rebuilt d
-            p = _project_conv(pl, d, act1, st1, gate, sv["wp"], stats=False)[0]
+            p = _project_conv(None, pl, d, act1, st1, gate, sv["wp"], stats=False)[0]
         # y = bn2(p) * rowscale + x
         dp, dg2, db2 = ops.bnact_bwd(p, n, ohw, a.cout, st2, blk._bn2.weight, 0, g=dy, rowscale=sv["rowscale"], frozen=frozen)
         # project 1x1: p = A1 . wp^T, A1 = silu(bn1(d)) * gate   (A1 is recomputed inside the wgrad GEMM)
@@ -475,11 +480,7 @@ class _MBConvFn(torch.autograd.Function):
                 del e, dw_in
                 _, dg0, db0 = ops.bn_bwd_coefs(part0, n * hw, st0, blk._bn0.weight, frozen=True)
                 ws_t = ops.bn_frozen_weight_t(blk._expand_conv.weight.view(a.cexp, a.cin), st0.scale)      # [cin, cexp]
-                if pl.xbwd:
-                    dx, dwe = ops.xbwd_rows(dz0, x, ws_t, residual=dy if a.skip else None)
-                else:
-                    dx = ops.linear_dgrad(dz0, sv["we"], residual=dy if a.skip else None, w_t=ws_t)
-                    dwe = ops.linear_wgrad(dz0, x)
+                dx, dwe = expand_bwd(dz0, ws_t)
                 dwe = ops.rowscale_f32_(dwe, st0.scale)
                 de = None
             elif pl.fold_bn0:
@@ -507,12 +508,7 @@ class _MBConvFn(torch.autograd.Function):
             del dd
         if a.expand != 1:
             if de is not None:
-                we_t = blk.w_expand(transposed=True)         # [cin, cexp]
-                if pl.xbwd:                                  # one pass over de for both gradients (round 5)
-                    dx, dwe = ops.xbwd_rows(de, x, we_t, residual=dy if a.skip else None)
-                else:
-                    dx = ops.linear_dgrad(de, sv["we"], residual=dy if a.skip else None, w_t=we_t)
-                    dwe = ops.linear_wgrad(de, x)
+                dx, dwe = expand_bwd(de, blk.w_expand(transposed=True))
             grads["_expand_conv.weight"] = dwe.view(a.cexp, a.cin, 1, 1)
             grads["_bn0.weight"], grads["_bn0.bias"] = dg0, db0
         else:
@@ -526,25 +522,25 @@ class _MBConvFn(torch.autograd.Function):
         grads["_project_conv.weight"] = dwp.view(a.cout, a.cexp, 1, 1)
         grads["_bn2.weight"], grads["_bn2.bias"] = dg2, db2
         ctx.saved = None
-        return (dx, None, None, None, None, None, None, None) + ops.deliver_param_grads(blk._params(), [grads[nm] for nm in blk._param_names])
+        return (dx,) + (None,) * 8 + ops.deliver_param_grads(ops.cached_params(blk), [grads[nm] for nm in blk._param_names])
 
 
 class _HeadFn(torch.autograd.Function):
     """_conv_head (1x1) + _bn1 + swish + global average pool [ref: efficientnet_custom.py:283, 307-309]."""
 
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, mod, n, h, wd):
+    def forward(ctx, x, w, gamma, beta, mod, n, h, wd, call):
         cin, cout = w.shape[1], w.shape[0]
         wb = ops.cast_bf16(w.view(cout, cin))
         if mod.fp8 and cin % 16 == 0:
             e, part = ops.linear_fwd_fp8(x, wb, stats=True)
         else:
-            e, part = _conv_stats(ops.linear_fwd, mod.batch_stats, x, wb)
-        st = _bn_stats(part, n * h * wd, mod._bn1, mod.batch_stats)
+            e, part = _conv_stats(call, ops.linear_fwd, mod.batch_stats, x, wb)
+        st = _bn_stats(call, part, n * h * wd, mod._bn1, mod.batch_stats)
         pooled = ops.bnact_pool(e, n, h * wd, cout, st.scale, st.shift, 1)
         ctx.mod, ctx.st, ctx.geo, ctx.frozen = mod, st, (n, h, wd, cin, cout), not mod.batch_stats
         ctx.save_for_backward(x, e, wb)
-        mod._head_cache = (e, st, n, h, wd, cout)
+        call.head = (e, st, n, h, wd, cout)
         return pooled
 
     @staticmethod
@@ -560,7 +556,7 @@ class _HeadFn(torch.autograd.Function):
         dw = ops.linear_wgrad(de, x)
         gw, gg, gb = ops.deliver_param_grads((mod._conv_head.weight, mod._bn1.weight, mod._bn1.bias),
                                              (dw.view(cout, cin, 1, 1), dgamma, dbeta))
-        return dx, gw, gg, gb, None, None, None, None
+        return dx, gw, gg, gb, None, None, None, None, None
 
 
 class _DropoutFn(torch.autograd.Function):
@@ -585,8 +581,6 @@ class _BN(nn.BatchNorm2d):
 
     def __init__(self, c):
         super().__init__(c, momentum=BN_MOMENTUM, eps=BN_EPS)
-        self.track_update = True          # engine may switch running-stat updates off for re-forward passes
-        self.defer_count = None           # list collecting the counters of one encoder forward (see EfficientNet.forward)
 
     def forward(self, x):                 # pragma: no cover
         raise RuntimeError("BatchNorm arithmetic runs inside the fused HIP kernels, not here")
@@ -718,29 +712,11 @@ class MBConvBlock(nn.Module):
         v = self._project_conv.weight.view(self.args.cout, self.args.cexp)
         return ops.cast_transpose_bf16(v) if transposed else ops.cast_bf16(v)
 
-    def _params(self):
-        """the block's Parameter objects in ``_param_names`` order (cached: ``named_parameters`` walks the module tree)"""
-        # cached with the (owner dict, key) slot of every parameter: a Parameter OBJECT survives .to() / load_state_dict (both
-        # write .data in place) but not ``module.weight = nn.Parameter(...)`` / ``load_state_dict(assign=True)`` / to_empty() --
-        # then the slots no longer hold the cached objects and the list is rebuilt (ADVICE r3: gradients must not go to
-        # orphaned Parameters)
-        cached = self.__dict__.get("_plist")
-        if cached is not None:
-            ps, slots = cached
-            for p_, (d_, k_) in zip(ps, slots):
-                if d_.get(k_) is not p_:
-                    cached = None
-                    break
-        if cached is None:
-            slots = [(m._parameters, k) for m in self.modules() for k, v in m._parameters.items() if v is not None]
-            ps = [d_[k_] for d_, k_ in slots]
-            assert len(ps) == len(self._param_names)
-            self.__dict__["_plist"] = (ps, slots)
-        return ps
-
-    def forward(self, inputs, n, h, w, rowscale=None, link=None):
-        """link: the ``_StemLink`` of a linked stem whose raw output this call reads (block 0); grad mode: see ``plan``"""
-        return _MBConvFn.apply(inputs, rowscale, self, n, h, w, torch.is_grad_enabled(), link, *self._params())
+    def forward(self, inputs, n, h, w, rowscale=None, link=None, call=None):
+        """link: the ``_StemLink`` of a linked stem whose raw output this call reads (block 0); call: the ``_Call`` of the encoder
+        forward this is part of (None: the block on its own); grad mode: see ``plan``"""
+        return _MBConvFn.apply(inputs, rowscale, self, n, h, w, torch.is_grad_enabled(), link,
+                               call if call is not None else _Call(), *ops.cached_params(self))
 
 
 class EfficientNet(nn.Module):
@@ -779,6 +755,10 @@ class EfficientNet(nn.Module):
         self.rng = _Seeds()
         self.register_buffer("_ones_b", torch.ones(1), persistent=False)
         self._bn_layers = [m for m in self.modules() if isinstance(m, _BN)]
+        # what reaches a forward through ``module(x)`` rather than as an argument; read by ``_new_call`` alone
+        self._tape = None                 # set_stat_tape
+        self.update_running = True        # False: forwards leave running statistics and batch counters alone (the engine's re-forwards)
+        self._side_defer = self._side_counters = None         # side_call_begin .. side_call_end
 
     # ---------------------------------------------------------------------------- construction API
     @classmethod
@@ -894,13 +874,12 @@ class EfficientNet(nn.Module):
         l, r, t, b = self.stem_pad
         return n, _out_extent(h, t, b, 3, 2), _out_extent(w, l, r, 3, 2)
 
-    def _stem(self, x):
+    def _stem(self, x, call=None):
         """stem of one chain -> (output, its _StemLink or None, output geometry).  Block 0 has no expand conv (every EfficientNet-
         B*): the stem's bn0 + swish then runs inside block 0's depthwise kernels, which get the link with the stem's RAW output"""
         b0 = self._blocks[0].args
         link = _StemLink() if (LINK_STEM and b0.expand == 1 and not b0.skip and b0.s == 1) else None
-        args = (x, self._conv_stem.weight, self._bn0.weight, self._bn0.bias, self)
-        y = _StemFn.apply(*args, link) if link is not None else _StemFn.apply(*args)
+        y = _StemFn.apply(x, self._conv_stem.weight, self._bn0.weight, self._bn0.bias, self, link, call)
         return y, link, self.stem_geo(x.shape[0], *x.shape[2:])
 
     def _drop_connect_scales(self, n, device, seed):
@@ -916,29 +895,37 @@ class EfficientNet(nn.Module):
             out.append(ops.dropout_f32(self._ones_b.expand(n).contiguous(), p, seed, 1000 + i))
         return out
 
-    def _features_nhwc(self, inputs):
+    def set_stat_tape(self, tape):
+        """install (or remove: None) the tape the next forwards of THIS encoder record on / replay from (engine._step_micro)"""
+        self._tape = tape
+
+    def _new_call(self, defer=None):
+        """the context of one chain of a forward that starts now (draws its seed); the one reader of the encoder's ambient state"""
+        held = self._side_counters
+        return _Call(self._tape, self.update_running, defer if defer is not None else self._side_defer,
+                     held if held is not None else [], self.rng.next())
+
+    def _end_call(self, call):
+        """bump the batch counters the call collected with one multi-tensor launch (116 one-element add launches per forward
+        otherwise) -- unless a side-call bracket holds them back for ``side_call_end``"""
+        if call.counters and call.counters is not self._side_counters:
+            with torch.no_grad():
+                torch._foreach_add_(call.counters, 1)
+
+    def _run(self, inputs):
+        """one forward on the current stream -> (pooled features before dropout, its ``_Call``)"""
         if not inputs.is_cuda:
             raise RuntimeError("mammo_clip_amd.EfficientNet runs only on a HIP device (no CPU fallback)")
         x = inputs if isinstance(inputs, ops.RawImages) or inputs.dtype == torch.float32 else inputs.float()
-        seed = self.rng.next()
-        self._last_seed = seed
-        # num_batches_tracked of the ~120 BatchNorm layers: collected during the forward, incremented by one
-        # multi-tensor launch at its end (116 one-element add launches per forward otherwise)
-        counters = [] if self.batch_stats else None
-        bns = self._bn_layers if counters is not None else ()
-        for bn in bns:
-            bn.defer_count = counters
-        try:
-            y, link, (n, h, w) = self._stem(x)
-            scales = self._drop_connect_scales(n, x.device, seed)
-            for blk, rs in zip(self._blocks, scales):
-                y = blk(y, n, h, w, rs, link if blk.args.idx == 0 else None)
-                n, h, w = blk.out_geo(n, h, w)
-        finally:
-            for bn in bns:
-                bn.defer_count = None
-        self._pending_counters = counters
-        return y, n, h, w
+        call = self._new_call()
+        y, link, (n, h, w) = self._stem(x, call)
+        scales = self._drop_connect_scales(n, x.device, call.seed)
+        for blk, rs in zip(self._blocks, scales):
+            y = blk(y, n, h, w, rs, link if blk.args.idx == 0 else None, call)
+            n, h, w = blk.out_geo(n, h, w)
+        pooled = _HeadFn.apply(y, self._conv_head.weight, self._bn1.weight, self._bn1.bias, self, n, h, w, call)
+        self._end_call(call)
+        return pooled, call
 
     # ---------------------------------------------------------------------------- side-stream calls (model/clip.py)
     def warm_weight_images(self, backward: bool):
@@ -965,18 +952,17 @@ class EfficientNet(nn.Module):
     def side_call_begin(self):
         """the next forward of this encoder runs on a side stream beside another one: BatchNorm running statistics and batch
         counters are left to ``side_call_end`` (after the join, on the main stream)"""
-        global _BN_DEFER
-        self._hold_counters = True
-        if self.batch_stats:
-            _BN_DEFER = _BNDefer(self)
+        self._side_counters = []
+        self._side_defer = _BNDefer(self) if self.batch_stats else None
 
     def side_call_end(self):
-        global _BN_DEFER
-        d, _BN_DEFER = _BN_DEFER, None
-        self._hold_counters = False
+        d, c = self._side_defer, self._side_counters
+        self._side_defer = self._side_counters = None
         if d is not None:
             d.apply()
-        self._flush_counters()
+        if c:
+            with torch.no_grad():
+                torch._foreach_add_(c, 1)
 
     def forward_pair(self, x1, x2, side):
         """Both image views of a batch [ref: clip.py:83,108 -- two sequential ``encode_image`` calls] as two chains issued
@@ -986,7 +972,6 @@ class EfficientNet(nn.Module):
         first), so every result equals two sequential calls; what changes is the ISSUE order -- the two chains are in flight
         side by side from the first launch on, in the forward and (autograd replays the creation order backwards) in the
         backward.  Returns the two pooled feature tensors."""
-        global _BN_DEFER
         if not (x1.is_cuda and x2.is_cuda):
             raise RuntimeError("mammo_clip_amd.EfficientNet runs only on a HIP device (no CPU fallback)")
         main = torch.cuda.current_stream(x1.device)
@@ -1002,85 +987,56 @@ class EfficientNet(nn.Module):
         for t_ in (x2.data if isinstance(x2, ops.RawImages) else x2,):
             if torch.is_tensor(t_) and t_.is_cuda:
                 t_.record_stream(side)          # allocated on the main stream, read by the side chain (allocator reuse)
-        seeds = [self.rng.next(), self.rng.next()]
-        training, bstat = self.training, self.batch_stats      # (stochastic pieces / BatchNorm on batch statistics)
-        counters = [[], []] if bstat else [None, None]
-        bns = self._bn_layers if bstat else ()
-        defer = None
-
         def chain(i):
-            """switch the issue point to chain i (stream, counter list, running-statistic target)"""
-            global _BN_DEFER
+            """switch the issue point to chain i"""
             torch.cuda.set_stream(side if i else main)
-            for bn in bns:
-                bn.defer_count = counters[i]
-            _BN_DEFER = defer if i else None
 
         ys, scales, links = [None, None], [None, None], [None, None]
         try:
-            torch.cuda.set_stream(side)
-            defer = _BNDefer(self) if bstat else None          # (zero-filled scratch: allocated and cleared on the side stream)
+            chain(1)
+            defer = _BNDefer(self) if self.batch_stats else None      # (zero-filled scratch: allocated and cleared on the side stream)
+            calls = [self._new_call(), self._new_call(defer)]         # (two consecutive seeds, view 1 first; one tape)
             for i in (0, 1):
                 chain(i)
-                ys[i], links[i], (n, h, w) = self._stem(xs[i])
-                scales[i] = self._drop_connect_scales(n, xs[i].device, seeds[i])
+                ys[i], links[i], (n, h, w) = self._stem(xs[i], calls[i])
+                scales[i] = self._drop_connect_scales(n, xs[i].device, calls[i].seed)
             for bi, blk in enumerate(self._blocks):
                 for i in (0, 1):
                     chain(i)
-                    ys[i] = blk(ys[i], n, h, w, scales[i][bi], links[i] if bi == 0 else None)
+                    ys[i] = blk(ys[i], n, h, w, scales[i][bi], links[i] if bi == 0 else None, calls[i])
                 n, h, w = blk.out_geo(n, h, w)
             pooled = [None, None]
             for i in (0, 1):
                 chain(i)
-                pooled[i] = _HeadFn.apply(ys[i], self._conv_head.weight, self._bn1.weight, self._bn1.bias, self, n, h, w)
-                if training and self._dropout_p > 0.0:
-                    pooled[i] = _DropoutFn.apply(pooled[i], self._dropout_p, seeds[i], 999)
+                pooled[i] = _HeadFn.apply(ys[i], self._conv_head.weight, self._bn1.weight, self._bn1.bias, self, n, h, w, calls[i])
+                if self.training and self._dropout_p > 0.0:
+                    pooled[i] = _DropoutFn.apply(pooled[i], self._dropout_p, calls[i].seed, 999)
         finally:
             torch.cuda.set_stream(main)
-            for bn in bns:
-                bn.defer_count = None
-            _BN_DEFER = None
-        self._last_seed = seeds[1]
         main.wait_stream(side)
         if defer is not None:
             defer.apply()
-        with torch.no_grad():
-            for c in counters:
-                if c:
-                    torch._foreach_add_(c, 1)
+        for c in calls:
+            self._end_call(c)
         pooled[1].record_stream(main)
         return pooled[0], pooled[1]
 
-    def _flush_counters(self):
-        if getattr(self, "_hold_counters", False):
-            return
-        c = getattr(self, "_pending_counters", None)
-        if c:
-            with torch.no_grad():
-                torch._foreach_add_(c, 1)
-        self._pending_counters = None
+    @staticmethod
+    def _feature_map(call):
+        """head conv + BN + swish of a finished call as an NCHW fp32 map"""
+        e, st, n, h, w, cout = call.head
+        fmap = ops.bnact_apply(e, n, h * w, cout, st.scale, st.shift, 1)
+        return ops.cast_f32(fmap).view(n, h, w, cout).permute(0, 3, 1, 2)
 
     def extract_features(self, inputs):
         """Final feature map after head conv + BN + swish, NCHW fp32 (API parity; not on the training hot path)."""
-        y, n, h, w = self._features_nhwc(inputs)
-        _HeadFn.apply(y, self._conv_head.weight, self._bn1.weight, self._bn1.bias, self, n, h, w)
-        self._flush_counters()
-        e, st, n, h, w, cout = self._head_cache
-        fmap = ops.bnact_apply(e, n, h * w, cout, st.scale, st.shift, 1)
-        return ops.cast_f32(fmap).view(n, h, w, cout).permute(0, 3, 1, 2)
+        return self._feature_map(self._run(inputs)[1])
 
     def forward(self, inputs):
         """[ref: efficientnet_custom.py:287-313]: pooled features [b, out_dim] (fp32); the dict form
         ``{"image": x}`` returns (pooled, raw_feature_map)."""
         want_map = isinstance(inputs, dict) and "image" in inputs
-        x = inputs["image"] if want_map else inputs
-        y, n, h, w = self._features_nhwc(x)
-        pooled = _HeadFn.apply(y, self._conv_head.weight, self._bn1.weight, self._bn1.bias, self, n, h, w)
-        self._flush_counters()
+        pooled, call = self._run(inputs["image"] if want_map else inputs)
         if self.training and self._dropout_p > 0.0:
-            pooled = _DropoutFn.apply(pooled, self._dropout_p, self._last_seed, 999)
-        if want_map:
-            e, st, n, h, w, cout = self._head_cache
-            fmap = ops.bnact_apply(e, n, h * w, cout, st.scale, st.shift, 1)
-            return pooled, ops.cast_f32(fmap).view(n, h, w, cout).permute(0, 3, 1, 2)
-        return pooled
+            pooled = _DropoutFn.apply(pooled, self._dropout_p, call.seed, 999)
+        return (pooled, self._feature_map(call)) if want_map else pooled

@@ -210,7 +210,7 @@ class _LayerFn(torch.autograd.Function):
             g[f"attention.self.{nm}.weight"] = dwqkv[i * H:(i + 1) * H]
             g[f"attention.self.{nm}.bias"] = dbqkv[i * H:(i + 1) * H]
         ctx.sv = None
-        return (dx, None, None, None, None, None, None) + ops.deliver_param_grads(lyr._params(), [g[nm] for nm in lyr._param_names])
+        return (dx, None, None, None, None, None, None) + ops.deliver_param_grads(ops.cached_params(lyr), [g[nm] for nm in lyr._param_names])
 
 
 # ---------------------------------------------------------------------------------------------- containers
@@ -259,27 +259,8 @@ class BertLayerHIP(nn.Module):
         self.hilo = False                  # two-term bf16 weight operands in the forward (BertModelHIP.set_hilo_weights)
         self._param_names = [n for n, _ in self.named_parameters()]
 
-    def _params(self):
-        # cached with the (owner dict, key) slot of every parameter: a Parameter OBJECT survives .to() / load_state_dict (both
-        # write .data in place) but not ``module.weight = nn.Parameter(...)`` / ``load_state_dict(assign=True)`` / to_empty() --
-        # then the slots no longer hold the cached objects and the list is rebuilt (gradients must not go to
-        # orphaned Parameters)
-        cached = self.__dict__.get("_plist")
-        if cached is not None:
-            ps, slots = cached
-            for p_, (d_, k_) in zip(ps, slots):
-                if d_.get(k_) is not p_:
-                    cached = None
-                    break
-        if cached is None:
-            slots = [(m._parameters, k) for m in self.modules() for k, v in m._parameters.items() if v is not None]
-            ps = [d_[k_] for d_, k_ in slots]
-            assert len(ps) == len(self._param_names)
-            self.__dict__["_plist"] = (ps, slots)
-        return ps
-
     def forward(self, x, maskb, b, t, seed, pk=None):
-        return _LayerFn.apply(x, maskb, self, b, t, seed, pk, *self._params())
+        return _LayerFn.apply(x, maskb, self, b, t, seed, pk, *ops.cached_params(self))
 
 
 class _Embeddings(nn.Module):

@@ -473,7 +473,8 @@ def _step_micro_body(self, batch: Dict, k: int) -> Dict[str, torch.Tensor]:
     keys = ("image_embeddings", "text_embeddings", "text_embeddings2", "image_view_embeddings")
     keep = min(self.keep_graphs, k)            # micro-batches whose graph is kept (activation memory: `keep` micro-batches)
     counters, parts, tapes = [], [], []
-    set_tape = getattr(_encmod, "set_stat_tape", None) if self.stat_tapes else None
+    enc = getattr(model, "image_encoder", None)
+    set_tape = getattr(enc, "set_stat_tape", None) if self.stat_tapes else None
     with torch.no_grad():
         for mb in mbs[:k - keep]:
             counters.append((irng.calls, trng._calls))
@@ -490,7 +491,6 @@ def _step_micro_body(self, batch: Dict, k: int) -> Dict[str, torch.Tensor]:
     # and never forwarded again (k - keep extra forwards per step instead of k: at 4 micro-batches per GPU and keep = 1
     # that is 6 % of the step; keep = 2 needs the activations of two micro-batches, ~230 GB at 32 pairs each)
     lives = []
-    enc = getattr(model, "image_encoder", None)
     base_modes = None
     if self.keep_recompute is not None and parts and hasattr(enc, "set_recompute"):
         base_modes = [blk.recompute for blk in enc._blocks]
@@ -513,9 +513,8 @@ def _step_micro_body(self, batch: Dict, k: int) -> Dict[str, torch.Tensor]:
     loss_dict = self.loss_func(**outputs, is_train=True)
     self._backward(lambda: self._seed(loss_dict["total"]).backward())   # d loss / d embeddings of the re-run micro-batches, full backward of the kept ones
     del out, lives, full, outputs
-    bns = [m for m in model.modules() if hasattr(m, "track_update")]
-    for m in bns:
-        m.track_update = False
+    if hasattr(enc, "update_running"):             # the re-forwards leave running statistics and batch counters alone
+        enc.update_running = False
     try:
         for i, mb in enumerate(mbs[:k - keep]):
             irng.calls, trng._calls = counters[i]
@@ -536,8 +535,8 @@ def _step_micro_body(self, batch: Dict, k: int) -> Dict[str, torch.Tensor]:
             ks = list(leaf)
             self._backward(lambda: torch.autograd.backward([out[kk] for kk in ks], [leaf[kk].grad[i * b:(i + 1) * b] for kk in ks]))
     finally:
-        for m in bns:
-            m.track_update = True
+        if hasattr(enc, "update_running"):
+            enc.update_running = True
         irng.calls, trng._calls = after
     self._grads_done(hooked=self.overlap_micro)
     self._optimizer_step()

@@ -1769,6 +1769,28 @@ class GradSink:
 GRAD_SINK = None
 
 
+def cached_params(mod):
+    """the Parameter objects of ``mod`` in ``mod._param_names`` (= named_parameters) order (cached: ``named_parameters`` walks
+    the module tree); what an autograd function of a whole block / layer takes as inputs and delivers gradients to"""
+    # cached with the (owner dict, key) slot of every parameter: a Parameter OBJECT survives .to() / load_state_dict (both
+    # write .data in place) but not ``module.weight = nn.Parameter(...)`` / ``load_state_dict(assign=True)`` / to_empty() --
+    # then the slots no longer hold the cached objects and the list is rebuilt (ADVICE r3: gradients must not go to
+    # orphaned Parameters)
+    cached = mod.__dict__.get("_plist")
+    if cached is not None:
+        ps, slots = cached
+        for p_, (d_, k_) in zip(ps, slots):
+            if d_.get(k_) is not p_:
+                cached = None
+                break
+    if cached is None:
+        slots = [(m._parameters, k) for m in mod.modules() for k, v in m._parameters.items() if v is not None]
+        ps = [d_[k_] for d_, k_ in slots]
+        assert len(ps) == len(mod._param_names)
+        mod.__dict__["_plist"] = (ps, slots)
+    return ps
+
+
 def deliver_param_grads(params, grads):
     """backward functions: hand ``grads`` (same order as ``params``) to the installed sink and return Nones for autograd,
     or return them unchanged when no sink is installed"""

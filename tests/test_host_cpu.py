@@ -665,14 +665,108 @@ def test_side_view_running_statistics_are_applied_in_the_reference_order():
     # side_call_begin / side_call_end bracket: counters are held back, the deferral object is installed only in training mode
     enc.eval()
     enc.side_call_begin()
-    assert ec._BN_DEFER is None and enc._hold_counters
+    assert enc._side_defer is None and enc._side_counters == []
+    assert enc._new_call().counters is enc._side_counters      # (held: a call inside the bracket collects into the bracket's list)
     enc.side_call_end()
-    assert not enc._hold_counters
+    assert enc._side_counters is None
     enc.train()
     enc.side_call_begin()
-    assert isinstance(ec._BN_DEFER, ec._BNDefer)
+    assert isinstance(enc._side_defer, ec._BNDefer) and enc._new_call().defer is enc._side_defer
     enc.side_call_end()
-    assert ec._BN_DEFER is None
+    assert enc._side_defer is None and enc._side_counters is None
+
+
+def test_encoder_call_context_host_logic(monkeypatch):
+    """``_Call``, the per-forward context of the image encoder: where a BatchNorm site's finalize launch sends its running-statistic
+    update, which batch counters the call collects, what a statistics tape records and replays -- and that all of it lives in the
+    context, so a forward that dies half-way leaves nothing on the encoder or its layers.  Host logic only: ops.bn_finalize /
+    ops.bn_eval_coeffs are recording stubs."""
+    from mammo_clip_amd.breastclip.model.modules import efficientnet_custom as ec
+    enc = load_image_encoder({"source": "cnn", "name": "tf_efficientnetv2-detect", "pretrained": False, "model_type": "cnn"})
+    bns = enc._bn_layers[:4]
+    fin, coef, fail_at = [], [], [None]
+
+    def bn_finalize(partials, count, w, b, rm, rv, momentum, eps, update):
+        if fail_at[0] == len(fin):
+            raise RuntimeError("finalize failed")
+        fin.append((rm, rv, update))
+        return object()
+    monkeypatch.setattr(ec.ops, "bn_finalize", bn_finalize)
+    monkeypatch.setattr(ec.ops, "bn_eval_coeffs", lambda w, b, rm, rv, eps: coef.append((rm, rv)) or "eval")
+    state = lambda: (dict(enc.__dict__), [sorted(bn.__dict__) for bn in enc._bn_layers])      # noqa: E731
+    clean = state()
+    # default context: the layer's own buffers, update on, the layer's counter collected
+    call = enc._new_call()
+    assert (call.tape, call.update_running, call.defer, call.counters, call.head) == (None, True, None, [], None)
+    for bn in bns:
+        ec._bn_stats(call, None, 8, bn, True)
+    assert all(rm is bn.running_mean and rv is bn.running_var and upd is True for (rm, rv, upd), bn in zip(fin, bns))
+    assert len(call.counters) == 4 and all(c is bn.num_batches_tracked for c, bn in zip(call.counters, bns))
+    # a side chain: the scratch slices of its _BNDefer, the layer marked used
+    d = ec._BNDefer(enc)
+    call, n0 = enc._new_call(d), len(fin)
+    for bn in bns[:2]:
+        ec._bn_stats(call, None, 8, bn, True)
+    for (rm, rv, upd), bn in zip(fin[n0:], bns):
+        o = d.offs[id(bn)]
+        assert upd is True and rm.data_ptr() == d.flat[o:].data_ptr() and rv.data_ptr() == d.flat[d.total + o:].data_ptr()
+        assert rm.shape == rv.shape == (bn.num_features,)
+    assert d.used == bns[:2] and len(call.counters) == 2
+    # updates off (the engine's re-forwards): update=False reaches the launch, no counter, the deferral object is ignored
+    d = ec._BNDefer(enc)
+    enc.update_running = False
+    call, n0 = enc._new_call(d), len(fin)
+    enc.update_running = True
+    ec._bn_stats(call, None, 8, bns[0], True)
+    assert fin[n0][0] is bns[0].running_mean and fin[n0][1] is bns[0].running_var and fin[n0][2] is False
+    assert call.counters == [] and d.used == []
+    # record, then replay: the identical objects in order, no launch; inactive sites run fn and stay off the tape
+    tape = ec.StatTape()
+    enc.set_stat_tape(tape)
+    call = enc._new_call()
+    rec = [ec._bn_stats(call, None, 8, bns[0], True), call.taped(True, lambda: "gram"), call.taped(True, lambda: "pooled"),
+           ec._bn_stats(call, None, 8, bns[1], True)]
+    assert call.taped(False, lambda: "off") == "off" and not call.replaying
+    assert tape.items == rec and len(call.counters) == 2
+    enc.set_stat_tape(tape.replay())
+    call, n0 = enc._new_call(), len(fin)
+    enc.set_stat_tape(None)
+
+    def never():
+        raise AssertionError("a replay computes nothing")
+    got = [ec._bn_stats(call, None, 8, bns[0], True), call.taped(True, never), call.taped(True, never),
+           ec._bn_stats(call, None, 8, bns[1], True)]
+    assert call.replaying and call.taped(False, lambda: "off") == "off"
+    assert all(g is r for g, r in zip(got, rec)) and tape.pos == len(tape.items) == 4
+    assert len(fin) == n0 and call.counters == []
+    # ... and a replay needs no statistics partials from the producers, a rebuild in the backward (no call) neither
+    prod = lambda *a, stats=False: ("y", "partials") if stats else "y"      # noqa: E731
+    assert ec._conv_stats(call, prod, True) == ("y", None) and ec._conv_stats(call, prod, False) == ("y", "partials")
+    assert ec._conv_stats(None, prod, True, stats=False) == ("y", None)
+    assert ec._conv_stats(enc._new_call(), prod, True) == ("y", "partials")
+    # running statistics (eval / frozen): bn_eval_coeffs on the buffers; tape and counters are left alone
+    tape = ec.StatTape()
+    call, n0 = ec._Call(tape=tape, counters=[]), len(fin)
+    assert ec._bn_stats(call, None, 8, bns[2], False) == "eval"
+    assert coef[-1][0] is bns[2].running_mean and coef[-1][1] is bns[2].running_var
+    assert len(fin) == n0 and tape.items == [] and tape.pos == 0 and call.counters == []
+    # a forward that dies half-way leaves nothing behind: the next context starts clean
+    tape, d = ec.StatTape(), ec._BNDefer(enc)
+    enc.set_stat_tape(tape)
+    call = enc._new_call(d)
+    enc.set_stat_tape(None)
+    fail_at[0] = len(fin) + 2
+    with pytest.raises(RuntimeError, match="finalize failed"):
+        for bn in bns:
+            ec._bn_stats(call, None, 8, bn, True)
+    assert len(call.counters) == 2 and len(tape.items) == 2 and len(d.used) == 3
+    after = state()
+    assert after[1] == clean[1] and after[0].keys() == clean[0].keys()
+    assert all(after[0][k] is clean[0][k] for k in clean[0])
+    assert not any(hasattr(enc, a) for a in ("_head_cache", "_last_seed", "_pending_counters", "_hold_counters"))
+    assert not any(hasattr(bn, a) for bn in enc._bn_layers for a in ("track_update", "defer_count"))
+    call = enc._new_call()
+    assert (call.tape, call.update_running, call.defer, call.counters, call.head) == (None, True, None, [], None)
 
 
 # ------------------------------------------------------------------------------------------------ world_size = 2: the N = 8 step policy

@@ -464,6 +464,46 @@ def test_micro_batched_step_matches_full_graph():
         assert torch.equal(v, ref_buf[n]), n
 
 
+def test_stat_tape_belongs_to_one_encoder():
+    """A statistics tape is installed on ONE encoder (``EfficientNet.set_stat_tape``): a second encoder forwarded while it is
+    installed neither records on it nor sees it, and the first encoder's replayed re-forward reproduces its first forward bit
+    for bit.  Two B2 encoders in train() mode, 2 images of the B2 fixture's size."""
+    from mammo_clip_amd.breastclip.model.modules import efficientnet_custom as ec
+    _, H, W, T = [int(v) for v in np.load(os.path.join(GOLDEN, "e2e_b2_cfg1.npz"))["meta"]]
+    sd = ow.synth_state_dict(ow.efficientnet_shapes(oarch.build_arch("efficientnet-b2")), seed=10)
+    x = ow.synth_batch(2, H, W, T, seed=10)["images"].to(DEV)
+    A, B = (ec.EfficientNet.from_name("efficientnet-b2") for _ in range(2))
+    for enc in (A, B):
+        enc.load_state_dict(sd, strict=True)
+        enc.to(DEV).train()
+    with torch.no_grad():
+        y_plain = B(x)                                   # no tape anywhere
+        B.rng.calls = 0                                  # (same drop-connect / dropout masks again)
+        tape = ec.StatTape()
+        A.set_stat_tape(tape)
+        try:
+            y_b = B(x)
+            y_a = A(x)
+            # one forward's entries: every BatchNorm site, and per block the Gram pair of a fused expand + depthwise launch, the
+            # pooled means where the squeeze pass produces nothing else, the gate
+            want, (n, h, w) = len(A._bn_layers), A.stem_geo(*x.shape[:1], *x.shape[2:])
+            for blk in A._blocks:
+                pl = blk.plan(n, h, w, False)
+                want += int(pl.xdw) + int(not pl.keep_act) + 1
+                n, h, w = blk.out_geo(n, h, w)
+            assert len(tape.items) == want and tape.pos == 0
+            A.rng.calls = 0
+            A.set_stat_tape(tape.replay())
+            y_a2 = A(x)
+        finally:
+            A.set_stat_tape(None)
+    assert tape.pos == len(tape.items) == want
+    assert torch.equal(y_a2, y_a) and torch.equal(y_b, y_plain)
+    assert torch.equal(y_a, y_b)                         # (same weights, input and seed: the tape changes no value)
+    # (a replay launches no finalize: no running-statistic update, no count)
+    assert int(A._bn0.num_batches_tracked) == 1 and int(B._bn0.num_batches_tracked) == 2
+
+
 def test_fp8_pointwise_convs_config5():
     """BASELINE config #5 arithmetic: the late-stage 1x1 convolutions (expand / project / head on the tiled MFMA path) with
     per-tensor-scaled OCP e4m3 activations and weights.  Same weights and batch as the B5 golden case: the fp8 model must
