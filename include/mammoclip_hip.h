@@ -320,21 +320,27 @@ int mc_dwconv_bwd_data_xw_preferred(const mc_dwconv_args* args);
  * (Environment variable MC_DW_LANE sets the initial mode.)  Both forms produce bit-identical outputs. */
 int mc_dwconv_set_lane_mode(int mode);
 int mc_dwconv_lane_supported(const mc_dwconv_args* args);
-/* Round 5 -- the whole backward of a STRIDE-1 3x3 depthwise conv whose input was silu(bn0(e)) in ONE launch
+/* Round 5 -- the whole backward of a STRIDE-1 3x3 / 5x5 depthwise conv whose input was silu(bn0(e)) in ONE launch
  * [ref: efficientnet_custom.py:104-111 backwards: _depthwise_conv, _bn0 + swish]: the data gradient with the BatchNorm0
  * epilogue of mc_dwconv_fwd(epi_x) AND the weight gradient of mc_dwconv_bwd_weight from one staging of (dd, e) -- dd and e
  * are read once, dZ0 is written once (3 passes over the expanded tensor instead of 5).  The argument block is the one of
  * the data-gradient launch (x = dd [n, h, w, c] on the conv's OUTPUT geometry, w_kkc = the taps rotated by 180 degrees,
  * pad = k-1-pad, (oh, ow) = the conv's input geometry, epi_* = e and its BatchNorm statistics, out = dZ0, stat_partials
  * with mc_dwconv_bwd_fused_stat_rows() rows) plus dw_out: f32 [k*k][c], accumulated into (+=) in the conv's OWN tap order.
- * _supported: 3x3, stride 1, c % 8 == 0, epi_x given (the 5x5 form does not fit a wave's registers: see conv_lane.hip).
- * _preferred: the shapes on which this launch measured faster than the two it replaces. */
+ * The launch and its sizing helpers take 3x3 and 5x5.  The 5x5 launch runs 12-wave workgroups on 24-channel tiles (its 50 tap
+ * accumulators and the windows do not fit the 128 registers of a 16-wave workgroup: see conv_lane.hip); both weight-gradient
+ * endings (atomic, dw_partials) exist for it; the xw form below is 3x3 only.
+ * mc_dwconv_bwd_fused_supported: 3x3, stride 1, c % 8 == 0, epi_x given (it answers for the 3x3 instances only, as before).
+ * mc_dwconv_bwd_fused5_supported: the same for 5x5 (no xw).
+ * _preferred / fused5_preferred: the shapes on which the launch measured faster than the two it replaces. */
 /* Round 6: with args->xw (+ cin <= 64) the launch does not READ e: epi_x is the block input x and e = x . xw^T is formed per
  * 16-pixel group on the MFMA unit while the rows are staged (the staging of mc_mbconv_xdw_fwd, raw e rounded once to 16 bits
  * like the tensor the expand GEMM stores).  Together with mc_mbconv_xdw_fwd and the folded BatchNorm0 backward
  * (mc_bn_fold_*) the expanded tensor of a stride-1 3x3 block then never exists in HBM, forward or backward. */
 int mc_dwconv_bwd_fused_supported(const mc_dwconv_args* args);
 int mc_dwconv_bwd_fused_preferred(const mc_dwconv_args* args);
+int mc_dwconv_bwd_fused5_supported(const mc_dwconv_args* args);
+int mc_dwconv_bwd_fused5_preferred(const mc_dwconv_args* args);
 int mc_dwconv_bwd_fused_stat_rows(const mc_dwconv_args* args);
 int mc_dwconv_bwd_fused(const mc_dwconv_args* args, void* stream);
 /* Round 6 -- expand 1x1 conv -> BatchNorm0 + swish -> depthwise k x k conv of an MBConv block in ONE launch

@@ -454,8 +454,9 @@ class _MBConvFn(torch.autograd.Function):
         wflip = blk.w_taps(flipped=True) if s == 1 else None   # 180 degree rotation
         # round 5: stride-1 3x3 blocks run the WHOLE depthwise backward as one launch (conv_lane.hip MODE 3): data gradient with
         # the bn0 + swish epilogue AND the weight gradient from one staging of (dd, e) -- 3 passes over the expanded tensor
-        # instead of 5; where that launch is not preferred: weight gradient + data gradient as two launches
-        if not (pl.fused_dw or pl.efree_s2):
+        # instead of 5; where that launch is not preferred: weight gradient + data gradient as two launches.  fused_dw5: the same
+        # launch for the stride-1 5x5 blocks (12-wave instances), asked for through predicates of its own
+        if not (pl.fused_dw or pl.fused_dw5 or pl.efree_s2):
             dwdw = ops.dwconv_bwd_weight(dw_in, dd, *pl.dw, pro=pro0)
         grads = {}
         if a.expand != 1:
@@ -464,7 +465,7 @@ class _MBConvFn(torch.autograd.Function):
             # separate reduce pass over (e, dA0) is gone and the apply pass is a plain linear combination (stride 1: the
             # forward kernel on flipped taps; stride 2, round 3: the marching super-pixel kernel -- dA0 of the stride-2
             # blocks, the largest tensors of the network, is never written)
-            if pl.fused_dw:
+            if pl.fused_dw or pl.fused_dw5:
                 dz0, part0, dwdw = ops.dwconv_bwd_fused(dd, e, st0, wflip, n, h, w, a.cexp, k, l, t, oh, ow,
                                                         xw=(x, sv["we"]) if pl.efree else None)
             elif pl.efree_s2:
@@ -600,7 +601,7 @@ _Geo = namedtuple("_Geo", ["idx", "expand", "k", "s", "cin", "cexp", "cout", "cs
 # one call of an MBConv block (MBConvBlock.plan); dw = (n, h, w, cexp, k, s, pad_l, pad_t, oh, ow), the argument run of ops.dwconv_*
 _Plan = namedtuple("_Plan", ["n", "h", "w", "oh", "ow", "training", "xdw", "efree", "fp8_expand", "keep_act", "fp8_project",
                              "store_e", "store_d", "store_p", "fuse_proj_dgrad", "fused_dw", "fold_bn0", "xbwd", "dw", "efree_s2",
-                             "batch_stats"])
+                             "batch_stats", "fused_dw5"])
 # training: the module's mode (stochastic pieces, the statistics tape's squeeze-excite entries); batch_stats: BatchNorm on batch
 # statistics = training and not frozen (statistics epilogues, finalize, running-statistic updates, Gram pairs and every path whose
 # backward reads them).  Frozen (batch_stats off) the backward is the running-statistics one: dx = scale*dz at every site
@@ -679,10 +680,11 @@ class MBConvBlock(nn.Module):
         # ... and where no backward needs e stored (no graph, or a recompute mode that rebuilds it) the forward is fused too
         xdw = efree or (fusable and (rc >= 1 or not recording))
         keep_act = not ops._rows_ok(orows, a.cout, a.cexp, None, 0)
-        fold = fused_dw = fuse_proj = xbwd = False
+        fold = fused_dw = fused_dw5 = fuse_proj = xbwd = False
         if recording:
             fuse_proj = bool(FUSE_PROJ_DGRAD and ops.proj_dgrad_fusable(orows, a.cexp, a.cout, oh * ow))
             fused_dw = efree or bool(FUSE_DW_BWD and expand and ops.dwconv_bwd_fused_ok(*dw))
+            fused_dw5 = bool(FUSE_DW_BWD and expand and ops.dwconv_bwd_fused5_ok(*dw))
             fold = expand and bstat and (efree or 2 * rows * a.cexp >= (BN_FOLD_MIN_BYTES if a.s == 1 else max(BN_FOLD_MIN_BYTES, BN_FOLD_S2_MIN_BYTES)))
             xbwd = expand and not fold and ops.xbwd_rows_ok(rows, a.cexp, a.cin)
         # stride-2 3x3 blocks whose e is not stored (recompute modes >= 1): the backward forms the e rows from x inside the data-
@@ -694,7 +696,7 @@ class MBConvBlock(nn.Module):
                      keep_act=keep_act, fp8_project=keep_act and self.fp8 and a.cexp % 16 == 0 and a.cout > 64,
                      store_e=expand and rc == 0 and not xdw, store_d=rc < 2, store_p=rc < 4,
                      fuse_proj_dgrad=fuse_proj, fused_dw=fused_dw, fold_bn0=fold, xbwd=xbwd, dw=dw, efree_s2=efree_s2,
-                     batch_stats=bstat)
+                     batch_stats=bstat, fused_dw5=fused_dw5)
 
     def w_expand(self, transposed=False):
         """cached 16-bit image of the expand conv's weight, [cexp, cin] or transposed.  (Forward, backward and

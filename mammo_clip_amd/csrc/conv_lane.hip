@@ -20,6 +20,9 @@
 //   * work is cut into per-workgroup ranges of "virtual rows" (image, strip, output row) of equal length, so every CU
 //     gets the same number of rows whatever the image count; the two 32-channel tiles that share a 128-byte line run on
 //     the same XCD (same L2).
+// The fused 5x5 backward (MODE 3, K = 5) is the one exception to the 16-wave workgroup: 12 waves on a 24-channel tile (168 VGPRs
+// per lane, three waves per SIMD); a 128-byte line then holds pieces of up to four tiles, which the contiguous unit ranges per
+// XCD (xmap) keep in one L2.
 // The accumulator rotation is static: a block is RB = 4 input rows, the rotation period P = A*S rows, and the interval
 // body is unrolled over the U = P / gcd(RB, P) phases.
 #include "common_hip.h"
@@ -35,9 +38,11 @@ constexpr int gcd_c(int a, int b) { return b == 0 ? a : gcd_c(b, a % b); }
 // G > 1 ("several images per wave", narrow maps): the 64 lanes of a wave are G groups of LPI = 64 / G lanes, group g works on
 // image g of a group of G consecutive images -- a 57- or 29-column map then still fills the wave with two output columns per
 // lane.  A staged row is G segments (one per image, each with its own K-1 column halo); the work unit is (image group, row).
-template <int K, int S, int NCOL, int G = 1> struct Cfg {
+// W = waves per workgroup = channel pairs per tile.  16 everywhere but the fused 5x5 backward (waves_for below): 12 waves leave
+// a lane 168 VGPRs instead of 128, the tile is 24 channels (3 vectors per staged pixel, PXD = 13 stays odd).
+template <int K, int S, int NCOL, int G = 1, int W = 16> struct Cfg {
     static constexpr int K_ = K, S_ = S, NCOL_ = NCOL, G_ = G;
-    static constexpr int WAVES = 16;
+    static constexpr int WAVES = W;
     static constexpr int NT = WAVES * 64;
     static constexpr int TCH = 2 * WAVES;               // channels per tile: one channel pair per wave
     static constexpr int VPP = TCH / 8;                 // 16-byte vectors per staged pixel
@@ -75,7 +80,12 @@ template <int K, int S, int NCOL, int G = 1> struct Cfg {
     static_assert(RB % S == 0 && (K - 1) % S == 0, "block / tap geometry");
     static_assert(TOW <= LPI * NCOL, "a group's lanes cover its segment");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+    static_assert(W == 16 || W == 12 || W == 8, "workgroup width: 4, 3 or 2 waves per SIMD");
+    static_assert((RB * IWMAX * VPP) % NT == 0, "a block's staged vectors are whole rounds of the workgroup");
 };
+// The workgroup width of an instantiation is a function of (K, S, MODE): the kernel's template arguments -- and with them the
+// names and the code of every 16-wave instantiation -- stay what they were.
+constexpr int waves_for(int K, int S, int MODE_) { return (K == 5 && S == 1 && (MODE_ & 7) == 3) ? 12 : 16; }
 
 // Block descriptors live in LDS (a ring of 128, refilled 64 at a time by the lanes of wave 0 from a closed form of
 // block index -> (item, block)); everybody reads the few fields a pipeline stage needs when it needs them -- no long-lived
@@ -112,9 +122,9 @@ constexpr int NDESC = 128;
 // MODE_ = MODE, + 8 for the instantiations of MODE 2 / 3 / 5 whose weight gradient takes the store-and-sum ending (p.dw_partials,
 // no float atomics): separate instantiations, so the atomic ending keeps its code and its registers
 template <int K, int S, int NCOL, int MODE_, int G, int KC = 0>
-__global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwconv_args p, int strips, int nunits, int cpairs,
-                                                                  int ctiles, int ymax, int xmap) {
-    using C = Cfg<K, S, NCOL, G>;
+__global__ __launch_bounds__(64 * waves_for(K, S, MODE_), waves_for(K, S, MODE_) / 4) void dwconv_lane_fwd_kernel(
+    const mc_dwconv_args p, int strips, int nunits, int cpairs, int ctiles, int ymax, int xmap) {
+    using C = Cfg<K, S, NCOL, G, waves_for(K, S, MODE_)>;
     // MODE 5 (round 6): MODE 3 whose e rows -- the expand conv's output at the output positions, read for silu'(bn0(e)), the
     // BatchNorm0 reductions and a0 = silu(bn0(e)) of the weight gradient -- are FORMED from the block input x (epi_x = x
     // [n, oh, ow, cin], xw = the expand weight) by the MFMA staging of MODE 4 instead of being read: with MODE 4 in the forward
@@ -127,6 +137,7 @@ __global__ __launch_bounds__(1024, 4) void dwconv_lane_fwd_kernel(const mc_dwcon
     constexpr bool FUSED = MODE == 3 || XE;
     constexpr bool XF = MODE == 4;
     static_assert(!(XF || XE) || (KC >= 1 && KC <= 4), "MODE 4 / 5: cin <= 128");
+    static_assert(!(XF || XE) || C::WAVES == 16, "MODE 4 / 5: the MFMA staging forms 32-channel tiles");
     constexpr bool EPI = MODE == 1 || FUSED, BWW = MODE == 2, ETILE = EPI || BWW;       // ETILE: a second global tensor staged beside the input
     static_assert(!EPI || S == 1, "the BatchNorm-backward epilogue is provided for stride 1");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -868,6 +879,7 @@ template <typename C> Plan plan(const mc_dwconv_args& p) {
 
 template <typename C, int MODE, int KC = 0, bool DWS = false> int launch(const mc_dwconv_args& p, hipStream_t st) {
     static unsigned long long attr_done = 0;
+    static_assert(C::WAVES == waves_for(C::K_, C::S_, MODE), "the plan and the kernel agree on the workgroup width");
     auto kern = dwconv_lane_fwd_kernel<C::K_, C::S_, C::NCOL_, MODE + (DWS ? 8 : 0), C::G_, KC>;
     constexpr int lds = MODE == 3 ? C::LDS_BYTES_FUSED : (MODE == 4 ? C::LDS_BYTES + KC * 2048 : (MODE == 5 ? C::LDS_BYTES_FUSED + KC * 2048 : C::LDS_BYTES));
     static_assert(lds <= 160 * 1024, "LDS budget");
@@ -893,8 +905,9 @@ template <int K, int S, int MODE, typename F> auto pick(const mc_dwconv_args& p,
     // (its third LDS tile -- the e rows -- does not fit beside two-column input / output tiles)
     constexpr bool one_col = (S == 2) || (MODE == 2 && K == 5) || MODE == 3 || MODE == 5;
     if constexpr (one_col) {
-        if (gmax1() >= 2 && p.n >= 2 && p.ow <= Cfg<K, S, 1, 2>::TOW && g_fits(p, 2)) return f(Cfg<K, S, 1, 2>{});
-        return f(Cfg<K, S, 1, 1>{});
+        constexpr int W = waves_for(K, S, MODE);
+        if (gmax1() >= 2 && p.n >= 2 && p.ow <= Cfg<K, S, 1, 2, W>::TOW && g_fits(p, 2)) return f(Cfg<K, S, 1, 2, W>{});
+        return f(Cfg<K, S, 1, 1, W>{});
     } else {
         // several images per wave for maps that do not fill 64 lanes x 2 columns (MC_DW_LANE_G=1 switches it off for A/B)
         static const int gmax = gmax1();
@@ -948,24 +961,28 @@ extern "C" int mc_dwconv_fwd_lane(const mc_dwconv_args* a, void* stream) {
 // ---- MODE 3: fused backward (stride 1).  Argument block = the data-gradient launch of MODE 1 (x = dd on the conv's OUTPUT
 // geometry as (h, w), flipped taps, pads K-1-pad, (oh, ow) = the conv's input geometry, epi_* = e and its BatchNorm
 // statistics) + dw_out [k*k][c] f32, accumulated into (+=, the conv's own tap order).
-// 3x3 only: the 5x5 form needs 50 tap accumulators + the two windows + the data gradient's partial rows in one wave --
-// ~177 live VGPRs against the 128 of a 16-wave workgroup (compiled and measured in round 5: 177-224 spilled registers); the
-// 5x5 backward stays two launches (MODE 1 + MODE 2).
+// 3x3: 16-wave workgroups on 32-channel tiles, like every other mode.  5x5: the 50 tap accumulators + the a0 / silu' / e windows +
+// the data gradient's partial rows are ~177 live VGPRs against the 128 of a 16-wave workgroup (round 5: 177-224 spilled
+// registers), so its instances run 12 waves on 24-channel tiles (lane::waves_for): 163-168 VGPRs, no scratch, three waves per
+// SIMD.  The form whose e rows are formed from the block input (xw) exists for 3x3 only: its MFMA staging forms 32-channel
+// tiles and its fragments have no registers beside the 50 accumulators.
 extern "C" int mc_dwconv_bwd_fused_lane_supported(const mc_dwconv_args* a) {
     const mc_dwconv_args& p = *a;
     // (round 6: xw != NULL -- epi_x is the block input x [n, oh, ow, cin] and the e rows are formed from it: cin <= 64)
     if (p.xw && !(p.cin > 0 && p.cin % 8 == 0 && p.cin <= 64)) return 0;
-    return mc_dwconv_lane_supported(a) && p.k == 3 && p.stride == 1 && p.epi_x != nullptr;
+    if (p.k == 5 && p.xw) return 0;
+    return mc_dwconv_lane_supported(a) && p.stride == 1 && p.epi_x != nullptr;
 }
 
 extern "C" int mc_dwconv_bwd_fused_lane_stat_rows(const mc_dwconv_args* a) {
     const mc_dwconv_args& p = *a;
+    if (p.k == 5) return lane::pick<5, 1, 3>(p, [&](auto cfg) { return lane::plan<decltype(cfg)>(p).ymax; });
     return lane::pick<3, 1, 3>(p, [&](auto cfg) { return lane::plan<decltype(cfg)>(p).ymax; });
 }
 
 extern "C" int mc_dwconv_bwd_fused_lane(const mc_dwconv_args* a, void* stream) {
     const mc_dwconv_args& p = *a;
-    MC_CHECK(mc_dwconv_bwd_fused_lane_supported(a), "dwconv_bwd_fused: stride-1 conv with the BatchNorm epilogue operands (epi_x) only");
+    MC_CHECK(mc_dwconv_bwd_fused_lane_supported(a), "dwconv_bwd_fused: stride-1 3x3 / 5x5 conv with the BatchNorm epilogue operands (epi_x) only; e rows from the block input (xw): 3x3, cin <= 64");
     MC_CHECK(p.x && p.w_kkc && p.out && p.dw_out, "dwconv_bwd_fused: null dd / w / out / dw_out");
     MC_CHECK(p.epi_scale && p.epi_shift && p.epi_mean && p.epi_invstd && p.stat_partials,
              "dwconv_bwd_fused: the BatchNorm-backward epilogue needs scale/shift/mean/invstd and stat_partials");
@@ -982,6 +999,10 @@ extern "C" int mc_dwconv_bwd_fused_lane(const mc_dwconv_args* a, void* stream) {
             if (p.dw_partials) return p.cin <= 32 ? lane::launch<Cf, 5, 1, true>(p, st) : lane::launch<Cf, 5, 2, true>(p, st);
             if (p.cin <= 32) return lane::launch<Cf, 5, 1>(p, st);
             return lane::launch<Cf, 5, 2>(p, st);
+        });
+    } else if (p.k == 5) {
+        e = lane::pick<5, 1, 3>(p, [&](auto cfg) {
+            return p.dw_partials ? lane::launch<decltype(cfg), 3, 0, true>(p, st) : lane::launch<decltype(cfg), 3>(p, st);
         });
     } else {
         e = lane::pick<3, 1, 3>(p, [&](auto cfg) {
@@ -1000,12 +1021,16 @@ extern "C" int mc_dwconv_bwd_weight_lane_dw_rows(const mc_dwconv_args* a) {
 
 // public names (include/mammoclip_hip.h).  _preferred: where the fused launch measured faster than the two launches it
 // replaces (scripts/dw_form_ab.py, 32 images; MC_DW_FUSED=0 never / =1 wherever supported, for A/B runs)
-extern "C" int mc_dwconv_bwd_fused_supported(const mc_dwconv_args* a) { return mc_dwconv_bwd_fused_lane_supported(a); }
+// mc_dwconv_bwd_fused_supported / _preferred answer for the 3x3 instances, as they always did; the 5x5 instances are asked for
+// through mc_dwconv_bwd_fused5_supported / _preferred.  The launch and the sizing helpers are common to both.
+static int dw_fused_mode() { static const int mode = [] { const char* e = getenv("MC_DW_FUSED"); return e ? atoi(e) : -1; }(); return mode; }
+extern "C" int mc_dwconv_bwd_fused_supported(const mc_dwconv_args* a) { return a->k == 3 && mc_dwconv_bwd_fused_lane_supported(a); }
+extern "C" int mc_dwconv_bwd_fused5_supported(const mc_dwconv_args* a) { return a->k == 5 && mc_dwconv_bwd_fused_lane_supported(a); }
 extern "C" int mc_dwconv_bwd_fused_stat_rows(const mc_dwconv_args* a) { return mc_dwconv_bwd_fused_lane_stat_rows(a); }
 extern "C" int mc_dwconv_bwd_fused(const mc_dwconv_args* a, void* stream) { return mc_dwconv_bwd_fused_lane(a, stream); }
 extern "C" int mc_dwconv_bwd_fused_preferred(const mc_dwconv_args* a) {
-    static const int mode = [] { const char* e = getenv("MC_DW_FUSED"); return e ? atoi(e) : -1; }();
-    if (mode == 0 || !mc_dwconv_bwd_fused_lane_supported(a)) return 0;
+    const int mode = dw_fused_mode();
+    if (mode == 0 || !mc_dwconv_bwd_fused_supported(a)) return 0;
     if (mode == 1) return 1;
     const mc_dwconv_args& p = *a;
     // measured (32 images, two launches under the form policy -> fused, ms): c = 768 at 95x57 0.347 -> 0.286, c = 1824 at 48x29
@@ -1013,6 +1038,17 @@ extern "C" int mc_dwconv_bwd_fused_preferred(const mc_dwconv_args* a) {
     // lose (c = 24 at 760x456: 0.711 -> 1.265 -- 48-byte pixels in 32-channel tiles)
     // (B2 at 912 x 912, c = 144 at 228 x 228: forcing the fused form everywhere it is supported 153.7 -> 152.9 ms per cfg2 step)
     return (p.ow >= 50 && p.c >= 128) || (p.ow <= 30 && p.n >= 2 && p.c >= 128);
+}
+extern "C" int mc_dwconv_bwd_fused5_preferred(const mc_dwconv_args* a) {
+    const int mode = dw_fused_mode();
+    if (mode == 0 || !mc_dwconv_bwd_fused5_supported(a)) return 0;
+    if (mode == 1) return 1;
+    const mc_dwconv_args& p = *a;
+    // (12-wave instances; 32 images, the two lane-form launches of the parent library -> fused, both library runs of a
+    // parent / new / parent / new sequence on one box, ms): c = 384 at 190x114 0.937, 0.916 -> 0.701, 0.690; c = 768 at 95x57 0.462,
+    // 0.451 -> 0.348, 0.335; c = 1056 at 95x57 0.622, 0.595 -> 0.519, 0.529; c = 1824 at 48x29 0.294, 0.291 -> 0.233, 0.235.  Nothing
+    // narrower than 384 channels and no 30-49 column map was measured: they keep the two launches
+    return p.c >= 384 && (p.ow >= 50 || (p.ow <= 29 && p.n >= 2));
 }
 
 extern "C" int mc_dwconv_bwd_weight_lane(const mc_dwconv_args* a, void* stream) {

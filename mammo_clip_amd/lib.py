@@ -151,6 +151,8 @@ _SIGS = {
     "mc_dwconv_lane_supported": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_fused_supported": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_fused_preferred": ([C.POINTER(DwconvArgs)], I),
+    "mc_dwconv_bwd_fused5_supported": ([C.POINTER(DwconvArgs)], I),
+    "mc_dwconv_bwd_fused5_preferred": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_fused_stat_rows": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_fused": ([C.POINTER(DwconvArgs), P], I),
     "mc_mbconv_xdw_supported": ([C.POINTER(DwconvArgs)], I),

@@ -788,6 +788,20 @@ def dwconv_bwd_fused_ok(n, h, w, c, k, stride, pad_l, pad_t, oh, ow, force=False
     return hit
 
 
+def dwconv_bwd_fused5_ok(n, h, w, c, k, stride, pad_l, pad_t, oh, ow, force=False):
+    """the same question for the 5x5 instances of the launch (mc_dwconv_bwd_fused5_supported / _preferred; geometry only, cached)"""
+    if stride != 1 or k != 5:
+        return False
+    key = (n, h, w, c, k, pad_l, pad_t, oh, ow, force, "5x5")
+    hit = _FUSED_OK.get(key)
+    if hit is None:
+        a = _dw_args(n, oh, ow, c, k, 1, k - 1 - pad_l, k - 1 - pad_t, h, w)
+        a.epi_x = 16                                    # any non-null value: only looked at
+        lib_ = L.load()
+        hit = _FUSED_OK[key] = bool(lib_.mc_dwconv_bwd_fused5_supported(C.byref(a)) if force else lib_.mc_dwconv_bwd_fused5_preferred(C.byref(a)))
+    return hit
+
+
 # stride-2 3x3 blocks whose backward neither rebuilds nor reads the expanded tensor (mc_dwconv_bwd_data with xw + dw_out, then the
 # folded BatchNorm0 backward), in the recompute modes that do not store e; 0 = off (A/B), 1 = where the library prefers the
 # launch, 2 = wherever it is supported (tests at small sizes)

@@ -1,7 +1,9 @@
 """Developer A/B of the two depthwise kernel forms (marching vs lane = column) on every depthwise shape of EfficientNet-B5 at
 1520x912, 32 images: forward with the BatchNorm+SiLU prologue + statistics, stride-1 data gradient with the BatchNorm-backward
 epilogue, weight gradient.  Prints ms per launch for both forms -- the table behind conv.hip::use_lane_fwd / use_lane_bww.
-usage: python scripts/dw_form_ab.py"""
+The last column is the fused backward launch (conv_lane.hip MODE 3: 3x3, and 5x5 on 12-wave workgroups) against the two launches
+under the policy's form choice, wherever the library supports it.
+usage: python scripts/dw_form_ab.py [k [stride]]      (only the shapes of that kernel size / stride)"""
 import os
 import sys
 
@@ -33,11 +35,13 @@ def timeit(fn, iters=4):
 arch = oarch.build_arch("efficientnet-b5")
 chain = oarch.spatial_chain(arch, 1520, 912)
 seen = set()
+only_k = int(sys.argv[1]) if len(sys.argv) > 1 else 0
+only_s = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 print("# k s c  in -> out      |  fwd+pro march / lane  |  dgrad+epi march / lane  |  wgrad march / lane  |  policy: dgrad+epi + wgrad -> fused backward   (ms per launch, 32 images)")
 for blk in arch.blocks:
     (h, w), (oh, ow) = chain[blk.idx], chain[blk.idx + 1]
     key = (blk.cexp, blk.k, blk.s, h, w)
-    if key in seen:
+    if key in seen or (only_k and blk.k != only_k) or (only_s and blk.s != only_s):
         continue
     seen.add(key)
     c, k, s = blk.cexp, blk.k, blk.s
@@ -59,7 +63,7 @@ for blk in arch.blocks:
     lib.mc_dwconv_set_lane_mode(-1)
     (f0, e0, g0), (f1, e1, g1) = res
     fused = ""
-    if s == 1 and ops.dwconv_bwd_fused_ok(n, h, w, c, k, s, l, t, oh, ow, force=True):
+    if s == 1 and (ops.dwconv_bwd_fused_ok(n, h, w, c, k, s, l, t, oh, ow, force=True) or ops.dwconv_bwd_fused5_ok(n, h, w, c, k, s, l, t, oh, ow, force=True)):
         # round 5: the two backward launches under the POLICY's form choice against the one fused launch (conv_lane.hip MODE 3)
         ep = timeit(lambda: ops.dwconv_bwd_data(dy, wk, n, h, w, c, k, 1, l, t, oh, ow, w_kkc_flipped=wflip, epi=(x, st)))
         gp = timeit(lambda: ops.dwconv_bwd_weight(x, dy, n, h, w, c, k, s, l, t, oh, ow, pro=(sc, sh)))
