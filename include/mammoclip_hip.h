@@ -312,6 +312,18 @@ int mc_dwconv_bwd_data_xw_supported(const mc_dwconv_args* args);
  * image, super-rows (2 input rows) per segment, channel tiles; returns mc_dwconv_bwd_data_stat_rows().  For tests that must
  * know a shape spans several strips / segments. */
 int mc_dwconv_bwd_data_plan(const mc_dwconv_args* args, int* plan);
+/* Two more host-only queries for tests that must know which tile seams a shape reaches (pure functions of the geometry fields;
+ * neither launches anything nor looks at the lane mode).
+ * mc_dwconv_march_plan: the marching forward (weight_grad == 0; with epi_x its stride-1 data-gradient form) or weight gradient:
+ * plan[6] = output columns per strip, channels per tile, column strips per row, row segments per image, output rows per
+ * segment, persistent workgroups per channel tile (= the return value: the rows of stat_partials / dw_partials of that form).
+ * mc_dwconv_lane_plan: the lane = column configuration for mode 0 (forward), 1 (stride-1 data gradient with the epilogue; the
+ * argument block of that launch), 2 (weight gradient), 3 (fused backward; the argument block of mc_dwconv_bwd_fused):
+ * plan[8] = images per wave, output columns per lane, output columns per strip, column strips per row, channel tiles, tile
+ * pairs, work units, y slots (= the return value: the rows of stat_partials / dw_partials of that form).
+ * Both return 0 for an argument block the form does not take. */
+int mc_dwconv_march_plan(const mc_dwconv_args* args, int weight_grad, int* plan);
+int mc_dwconv_lane_plan(const mc_dwconv_args* args, int mode, int* plan);
 int mc_dwconv_bwd_data_xw_preferred(const mc_dwconv_args* args);
 /* Two device forms of the forward / stride-1 data gradient exist: the "marching" kernels (a lane owns 2-4 channels, taps
  * in VGPRs) and the "lane = column" kernels of round 4 (a wave owns one channel pair, taps in SGPRs, 16-wave workgroups;

@@ -1352,6 +1352,22 @@ extern "C" int mc_dwconv_bwd_data_plan(const mc_dwconv_args* a, int* plan) {
     plan[0] = m.strips; plan[1] = m.segs; plan[2] = m.seg_rows; plan[3] = m.ctiles;
     return m.gy;
 }
+// the tile shape and the work split of the marching forward (weight_grad == 0; epi_x set: its stride-1 data-gradient form) or
+// weight gradient for THIS argument block, whatever the lane mode: plan[6] = output columns per strip, channels per tile, column
+// strips per row, row segments per image, output rows per segment, persistent workgroups per channel tile (= the return value,
+// the rows of stat_partials / dw_partials of the marching form); 0: not a depthwise shape.  Host arithmetic only.
+extern "C" int mc_dwconv_march_plan(const mc_dwconv_args* a, int weight_grad, int* plan) {
+    const mc_dwconv_args& p = *a;
+    if (!((p.k == 3 || p.k == 5) && (p.stride == 1 || p.stride == 2)) || p.n < 1 || p.c < 1 || p.oh < 1 || p.ow < 1) return 0;
+    auto fill = [&](auto cfg) {
+        using C = decltype(cfg);
+        const MarchPlan m = weight_grad ? march_bww_plan<C>(p) : march_plan<C>(p);
+        plan[0] = C::TOW; plan[1] = C::TCH; plan[2] = m.strips; plan[3] = m.segs; plan[4] = m.seg_rows; plan[5] = m.gy;
+        return m.gy;
+    };
+    if (p.k == 3) return p.stride == 1 ? march_dispatch<3, 1>(p, fill, true) : march_dispatch<3, 2>(p, fill, true);
+    return p.stride == 1 ? march_dispatch<5, 1>(p, fill, true) : march_dispatch<5, 2>(p, fill, true);
+}
 // rows of stat_partials written by mc_dwconv_bwd_data with the stride-2 BatchNorm-backward epilogue (epi_x set)
 extern "C" int mc_dwconv_bwd_data_stat_rows(const mc_dwconv_args* a) {
     int plan[4];

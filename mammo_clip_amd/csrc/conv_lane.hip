@@ -1019,6 +1019,25 @@ extern "C" int mc_dwconv_bwd_weight_lane_dw_rows(const mc_dwconv_args* a) {
     return lane::pick_ks<2>(p, [&](auto cfg) { return lane::plan<decltype(cfg)>(p).ymax; });
 }
 
+// the configuration and the work split the lane = column kernels choose for THIS argument block (include/mammoclip_hip.h): mode
+// 0 forward, 1 stride-1 data gradient with the epilogue, 2 weight gradient, 3 fused backward.  Host arithmetic only.
+extern "C" int mc_dwconv_lane_plan(const mc_dwconv_args* a, int mode, int* plan) {
+    const mc_dwconv_args& p = *a;
+    if (p.c < 1 || p.c % 8 != 0 || p.c > 8192 || p.n < 1 || p.oh < 1 || p.ow < 1) return 0;
+    if (!((p.k == 3 || p.k == 5) && (p.stride == 1 || p.stride == 2))) return 0;
+    if (mode < 0 || mode > 3 || ((mode == 1 || mode == 3) && p.stride != 1)) return 0;
+    auto fill = [&](auto cfg) {
+        using Cf = decltype(cfg);
+        const lane::Plan m = lane::plan<Cf>(p);
+        plan[0] = Cf::G_; plan[1] = Cf::NCOL_; plan[2] = Cf::TOW; plan[3] = m.strips; plan[4] = m.ctiles; plan[5] = m.cpairs;
+        plan[6] = m.nunits; plan[7] = m.ymax;
+        return m.ymax;
+    };
+    if (mode == 1) return p.k == 3 ? lane::pick<3, 1, 1>(p, fill) : lane::pick<5, 1, 1>(p, fill);
+    if (mode == 3) return p.k == 3 ? lane::pick<3, 1, 3>(p, fill) : lane::pick<5, 1, 3>(p, fill);
+    return mode == 0 ? lane::pick_ks<0>(p, fill) : lane::pick_ks<2>(p, fill);
+}
+
 // public names (include/mammoclip_hip.h).  _preferred: where the fused launch measured faster than the two launches it
 // replaces (scripts/dw_form_ab.py, 32 images; MC_DW_FUSED=0 never / =1 wherever supported, for A/B runs)
 // mc_dwconv_bwd_fused_supported / _preferred answer for the 3x3 instances, as they always did; the 5x5 instances are asked for

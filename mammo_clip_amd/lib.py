@@ -142,6 +142,8 @@ _SIGS = {
     "mc_dwconv_bwd_data": ([C.POINTER(DwconvArgs), P], I),
     "mc_dwconv_bwd_data_xw_supported": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_data_plan": ([C.POINTER(DwconvArgs), C.POINTER(C.c_int)], I),
+    "mc_dwconv_march_plan": ([C.POINTER(DwconvArgs), I, C.POINTER(C.c_int)], I),
+    "mc_dwconv_lane_plan": ([C.POINTER(DwconvArgs), I, C.POINTER(C.c_int)], I),
     "mc_dwconv_bwd_data_xw_preferred": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_weight": ([C.POINTER(DwconvArgs), P], I),
     "mc_dwconv_bwd_weight_dw_rows": ([C.POINTER(DwconvArgs)], I),
