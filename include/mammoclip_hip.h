@@ -563,6 +563,15 @@ int mc_attn_fwd(const mc_bf16* qkv, const float* mask_bias, int b, int t, int nh
 int mc_attn_bwd(const mc_bf16* qkv, const float* mask_bias, const mc_bf16* dctx, const float* lse, int b, int t,
                 int nh, float alpha, float p, unsigned long long seed, unsigned int stream_id, mc_bf16* dqkv,
                 void* stream);
+/* The same contract and arguments for 32 <= t <= 512, t % 32 == 0 (mc_attn_long_supported; attn.hip, long kernels): K / V
+ * whole in LDS in the forward, 256-row tiles restaged per chunk in the backward.  Same lse layout and dropout masks as
+ * mc_attn_fwd / mc_attn_bwd; the text encoder sends only t > 256 here. */
+int mc_attn_long_supported(int t, int head_dim);
+int mc_attn_long_fwd(const mc_bf16* qkv, const float* mask_bias, int b, int t, int nh, float alpha, float p,
+                     unsigned long long seed, unsigned int stream_id, mc_bf16* ctx, float* lse, void* stream);
+int mc_attn_long_bwd(const mc_bf16* qkv, const float* mask_bias, const mc_bf16* dctx, const float* lse, int b, int t,
+                     int nh, float alpha, float p, unsigned long long seed, unsigned int stream_id, mc_bf16* dqkv,
+                     void* stream);
 int mc_gelu_fwd(const mc_bf16* x, mc_bf16* y, long long n, void* stream);
 int mc_gelu_bwd(const mc_bf16* dy, const mc_bf16* x, mc_bf16* dx, long long n, void* stream);
 /* mask bias for attention: out[b, t] = (1 - mask[b,t]) * -3.0e38-ish (finfo.min)  */
@@ -593,6 +602,14 @@ int mc_attn_varlen_fwd(const mc_bf16* qkv, const int* cu_seqlens, const int* ord
 int mc_attn_varlen_bwd(const mc_bf16* qkv, const int* cu_seqlens, const int* order, const mc_bf16* dctx, const float* lse,
                        int b, int max_len, int t_pad, long long rows, int nh, float alpha, float p,
                        unsigned long long seed, unsigned int stream_id, mc_bf16* dqkv, void* stream);
+/* mc_attn_varlen_* for 1 <= len_i <= max_len <= 512 (mc_attn_varlen_long_supported; attn.hip, long kernels), same arguments */
+int mc_attn_varlen_long_supported(int max_len, int head_dim);
+int mc_attn_varlen_long_fwd(const mc_bf16* qkv, const int* cu_seqlens, const int* order, int b, int max_len, int t_pad,
+                            long long rows, int nh, float alpha, float p, unsigned long long seed, unsigned int stream_id,
+                            mc_bf16* ctx, float* lse, void* stream);
+int mc_attn_varlen_long_bwd(const mc_bf16* qkv, const int* cu_seqlens, const int* order, const mc_bf16* dctx, const float* lse,
+                            int b, int max_len, int t_pad, long long rows, int nh, float alpha, float p,
+                            unsigned long long seed, unsigned int stream_id, mc_bf16* dqkv, void* stream);
 /* mc_bert_embed_fwd / _bwd on packed rows [ref: transformers BertEmbeddings via text_encoder.py:47-49]: ids / tt in packed
  * order, pos_ids[r] = r - cu_seqlens[i]; alignment rows of y are zeros.  The backward accumulates (+=) like the padded one. */
 int mc_bert_embed_rows_fwd(const long long* ids, const long long* tt, const int* pos_ids, const int* row_map,

@@ -106,14 +106,23 @@ class _LayerFn(torch.autograd.Function):
                 y_ = ops.linear_fwd(inp, w_lo if w_lo is not None else ops.cast_bf16_lo(w_src), residual=y_)
             return y_
         qkv = lin(x, wqkv, bqkv, None, wqkv_lo)
+        long_attn = False      # the long kernels (257..512 keys)
         if pk is not None:
-            if not ops.attn_varlen_supported(pk.max_len, hd):
+            if ops.attn_varlen_supported(pk.max_len, hd):
+                ctxv, lse = ops.attn_varlen_fwd(qkv, pk, nh, hd ** -0.5, pa, seed, sid)
+            elif ops.attn_varlen_long_supported(pk.max_len, hd):
+                long_attn = True
+                ctxv, lse = ops.attn_varlen_long_fwd(qkv, pk, nh, hd ** -0.5, pa, seed, sid)
+            else:
                 raise RuntimeError(f"packed text encoder: no variable-length attention kernel for head size {hd}, length {pk.max_len}")
-            ctxv, lse = ops.attn_varlen_fwd(qkv, pk, nh, hd ** -0.5, pa, seed, sid)
             probs = pd = None
         elif ops.attn_supported(t, hd):
             # one kernel: scores, mask, softmax, dropout and context; only (row max, 1/row sum) are kept for backward
             ctxv, lse = ops.attn_fwd(qkv, maskb, b, t, nh, hd ** -0.5, pa, seed, sid)
+            probs = pd = None
+        elif ops.attn_long_supported(t, hd):
+            long_attn = True
+            ctxv, lse = ops.attn_long_fwd(qkv, maskb, b, t, nh, hd ** -0.5, pa, seed, sid)
             probs = pd = None
         else:
             lse = None
@@ -141,7 +150,7 @@ class _LayerFn(torch.autograd.Function):
         # hg = gelu(h1) is kept for the FFN2 weight gradient (100 MB per layer at 16384 rows: memory is not the constraint
         # of the text side, a recomputing GELU pass per layer and backward was)
         ctx.sv = dict(x=x, qkv=qkv, probs=probs, pd=pd, lse=lse, maskb=maskb, ctxv=ctxv, ao=ao, a=a, h1=h1, hg=hg, o=o, wqkv=wqkv, wo=wo, wi=wi, w2=w2,
-                      qkv_ver=ver,
+                      qkv_ver=ver, long_attn=long_attn,
                       ln1=(mean1, rstd1), ln2=(mean2, rstd2))
         return y
 
@@ -179,9 +188,11 @@ class _LayerFn(torch.autograd.Function):
         del dao
         # attention core
         if pk is not None:
-            dqkv = ops.attn_varlen_bwd(qkv, pk, dctx, sv["lse"], nh, hd ** -0.5, pa, seed, sid)
+            bwd = ops.attn_varlen_long_bwd if sv["long_attn"] else ops.attn_varlen_bwd
+            dqkv = bwd(qkv, pk, dctx, sv["lse"], nh, hd ** -0.5, pa, seed, sid)
         elif sv["lse"] is not None:
-            dqkv = ops.attn_bwd(qkv, sv["maskb"], dctx, sv["lse"], b, t, nh, hd ** -0.5, pa, seed, sid)
+            bwd = ops.attn_long_bwd if sv["long_attn"] else ops.attn_bwd
+            dqkv = bwd(qkv, sv["maskb"], dctx, sv["lse"], b, t, nh, hd ** -0.5, pa, seed, sid)
         else:
             dpd = torch.empty((b, nh, t, t), dtype=torch.float32, device=x.device)
             ops.gemm(dctx, qkv[:, 2 * H:], dpd, t, t, hd, H, 3 * H, t, c_f32=1, batch=b * nh, nb2=nh,
@@ -308,7 +319,8 @@ class BertModelHIP(nn.Module):
     def set_packed(self, on: bool = True):
         """Opt-in packed mode: a call whose attention masks are contiguous prefixes (1..10..0, what the tokenizer produces
         with padding="max_length") runs on the real tokens only -- the b reports concatenated into one [sum(len), H] row
-        matrix (ops.PackedRows), attention per sequence on its own length (mc_attn_varlen_*).  BERT couples tokens only through
+        matrix (ops.PackedRows), attention per sequence on its own length (mc_attn_varlen_*; mc_attn_varlen_long_* when a
+        report has more than 256 tokens).  BERT couples tokens only through
         attention and a padded key has probability exactly 0, so the real tokens' outputs, the loss and every gradient are
         those of the padded path; dropout draws the padded path's masks (same seeds, element indices of the padded layout).
         ``last_hidden_state`` then holds ZEROS at the padded positions (the padded path, like the reference, leaves

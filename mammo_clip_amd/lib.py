@@ -199,6 +199,9 @@ _SIGS = {
     "mc_attn_supported": ([I, I], I),
     "mc_attn_fwd": ([P, P, I, I, I, F, F, ULL, U, P, P, P], I),
     "mc_attn_bwd": ([P, P, P, P, I, I, I, F, F, ULL, U, P, P], I),
+    "mc_attn_long_supported": ([I, I], I),
+    "mc_attn_long_fwd": ([P, P, I, I, I, F, F, ULL, U, P, P, P], I),
+    "mc_attn_long_bwd": ([P, P, P, P, I, I, I, F, F, ULL, U, P, P], I),
     "mc_gelu_fwd": ([P, P, LL, P], I),
     "mc_gelu_bwd": ([P, P, P, LL, P], I),
     "mc_mask_bias": ([P, P, LL, P], I),
@@ -207,6 +210,9 @@ _SIGS = {
     "mc_attn_varlen_supported": ([I, I], I),
     "mc_attn_varlen_fwd": ([P, P, P, I, I, I, LL, I, F, F, ULL, U, P, P, P], I),
     "mc_attn_varlen_bwd": ([P, P, P, P, P, I, I, I, LL, I, F, F, ULL, U, P, P], I),
+    "mc_attn_varlen_long_supported": ([I, I], I),
+    "mc_attn_varlen_long_fwd": ([P, P, P, I, I, I, LL, I, F, F, ULL, U, P, P, P], I),
+    "mc_attn_varlen_long_bwd": ([P, P, P, P, P, I, I, I, LL, I, F, F, ULL, U, P, P], I),
     "mc_bert_embed_rows_fwd": ([P, P, P, P, P, P, P, P, P, F, LL, I, F, ULL, U, P, P, P, P], I),
     "mc_bert_embed_rows_bwd": ([P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, ULL, U, P, P, P, P, P, P], I),
     "mc_add_ln_rows_fwd": ([P, P, P, P, P, F, LL, I, F, ULL, U, P, P, P, P], I),

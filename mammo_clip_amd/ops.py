@@ -1283,6 +1283,29 @@ def attn_bwd(qkv, maskb, dctx, lse, b, t, nh, alpha, p, seed, sid):
     return dqkv
 
 
+def attn_long_supported(t, head_dim):
+    """Whether the long fused attention kernels (up to 512 keys) take this shape; the text encoder asks after attn_supported."""
+    if os.environ.get("MC_FUSED_ATTN", "1") == "0":      # the same developer switch: the unfused kernels
+        return False
+    return bool(L.load().mc_attn_long_supported(int(t), int(head_dim)))
+
+
+def attn_long_fwd(qkv, maskb, b, t, nh, alpha, p, seed, sid):
+    """attn_fwd for 32 <= t <= 512: same ctx, lse and dropout masks"""
+    ctx = empty((b * t, nh * 64), BF16, qkv)
+    lse = empty((b * nh * t, 2), torch.float32, qkv)
+    L.call("mc_attn_long_fwd", _p(qkv), _p(maskb), b, t, nh, float(alpha), float(p), int(seed), int(sid), _p(ctx), _p(lse), _st())
+    return ctx, lse
+
+
+def attn_long_bwd(qkv, maskb, dctx, lse, b, t, nh, alpha, p, seed, sid):
+    """attn_bwd for 32 <= t <= 512"""
+    dqkv = empty(qkv.shape, BF16, qkv)
+    L.call("mc_attn_long_bwd", _p(qkv), _p(maskb), _p(dctx), _p(lse), b, t, nh, float(alpha), float(p), int(seed), int(sid),
+           _p(dqkv), _st())
+    return dqkv
+
+
 def gelu_fwd(x):
     y = torch.empty_like(x)
     L.call("mc_gelu_fwd", _p(x), _p(y), x.numel(), _st())
@@ -1392,6 +1415,28 @@ def attn_varlen_fwd(qkv, pk, nh, alpha, p, seed, sid):
 def attn_varlen_bwd(qkv, pk, dctx, lse, nh, alpha, p, seed, sid):
     dqkv = empty(qkv.shape, BF16, qkv)
     L.call("mc_attn_varlen_bwd", _p(qkv), _p(pk.cu), _p(pk.order), _p(dctx), _p(lse), pk.b, pk.max_len, pk.t, pk.rows, nh,
+           float(alpha), float(p), int(seed), int(sid), _p(dqkv), _st())
+    return dqkv
+
+
+def attn_varlen_long_supported(max_len, head_dim):
+    """the long packed kernels (sequences of up to 512 tokens); packed rows have no unfused path, so no developer switch"""
+    return bool(L.load().mc_attn_varlen_long_supported(int(max_len), int(head_dim)))
+
+
+def attn_varlen_long_fwd(qkv, pk, nh, alpha, p, seed, sid):
+    """attn_varlen_fwd for pk.max_len <= 512"""
+    ctx = empty((pk.rows, nh * 64), BF16, qkv)
+    lse = empty((pk.rows, nh, 2), torch.float32, qkv)
+    L.call("mc_attn_varlen_long_fwd", _p(qkv), _p(pk.cu), _p(pk.order), pk.b, pk.max_len, pk.t, pk.rows, nh, float(alpha),
+           float(p), int(seed), int(sid), _p(ctx), _p(lse), _st())
+    return ctx, lse
+
+
+def attn_varlen_long_bwd(qkv, pk, dctx, lse, nh, alpha, p, seed, sid):
+    """attn_varlen_bwd for pk.max_len <= 512"""
+    dqkv = empty(qkv.shape, BF16, qkv)
+    L.call("mc_attn_varlen_long_bwd", _p(qkv), _p(pk.cu), _p(pk.order), _p(dctx), _p(lse), pk.b, pk.max_len, pk.t, pk.rows, nh,
            float(alpha), float(p), int(seed), int(sid), _p(dqkv), _st())
     return dqkv
 
