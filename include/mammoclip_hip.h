@@ -237,6 +237,27 @@ int mc_stem_im2col_u8(const unsigned char* x, long long sn, long long sc, long l
                       int pad_t, int oh, int ow, mc_bf16* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * direct stem convolution (csrc/stem.hip): the same 3x3 stride-2 conv without the patch matrix, for a CHANNELS-LAST
+ * image (element (img, y, x, c) at img*sn + y*sh + x*3 + c; fp32, or raw uint8 with the normalisation above).
+ *   fwd:   e[n*oh*ow, c0] bf16 = patches . wb[c0,32]^T (wb from mc_stem_weight_prep; 32 <= c0 <= 64, c0 % 8 == 0) -- the bits of
+ *          mc_stem_im2col + mc_gemm_rows_bf16; stat_partials (optional): [mc_stem_conv_blocks(n, oh, ow, 1)][2][c0] column sum /
+ *          sum of squares of e, the layout mc_bn_finalize reduces
+ *   wgrad: dw[c0,32] fp32 = de[n*oh*ow, c0]^T . patches (columns 27..31 zero); ws: [mc_stem_conv_blocks(n, oh, ow, 0 or 2)][c0][32]
+ *          floats of per-workgroup partials, summed in workgroup order (no atomics: the same bits every run).
+ *          bn_e / bn_coef (both or neither): `de` is dZ0 = dL/d bn0(e) and the kernel forms the BatchNorm0 backward apply
+ *          de = coef[0]*dZ0 + coef[1]*e + coef[2] (coef [3][c0] from mc_bn_bwd_finalize; rounded to 16 bits like the output of
+ *          mc_bnact_bwd_apply) while it stages dZ0: that pass and its tensor are not needed */
+int mc_stem_conv_blocks(int n, int oh, int ow, int kind);     /* kind: 0 wgrad, 1 fwd, 2 wgrad with bn_e / bn_coef */
+int mc_stem_conv_fwd(const float* x, long long sn, long long sh, int n, int h, int w, int pad_l, int pad_t, int oh,
+                     int ow, const mc_bf16* wb, int c0, mc_bf16* e, float* stat_partials, void* stream);
+int mc_stem_conv_fwd_u8(const unsigned char* x, long long sn, long long sh, const unsigned int* minmax, float mean,
+                        float std, int n, int h, int w, int pad_l, int pad_t, int oh, int ow, const mc_bf16* wb, int c0,
+                        mc_bf16* e, float* stat_partials, void* stream);
+int mc_stem_conv_wgrad(const void* x, int is_u8, long long sn, long long sh, const unsigned int* minmax, float mean,
+                       float std, int n, int h, int w, int pad_l, int pad_t, int oh, int ow, const mc_bf16* de, int c0,
+                       const mc_bf16* bn_e, const float* bn_coef, float* ws, float* dw, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * depthwise k x k convolution, NHWC bf16, static asymmetric zero padding
  * [ref: efficientnet_custom.py:109 (_depthwise_conv) + :110-111 (_bn1 statistics), :105-107 fused as
  *  prologue: x' = silu(x*pro_scale[c] + pro_shift[c]) applied to in-range inputs only]

@@ -219,6 +219,8 @@ def _no_fp8_frozen(mod):
 # expanded-tensor bytes per call from which the BatchNorm0 backward is folded into the expand conv's gradient GEMMs
 # (ops.bn_fold_expand_bwd) instead of running the apply pass; tests set it to 0 to exercise the folded path at small sizes
 LINK_STEM = os.environ.get("MC_LINK_STEM", "1") != "0"                  # stem bn0 + swish inside block 0's depthwise kernels (_StemLink)
+STEM_DIRECT = os.environ.get("MC_STEM_DIRECT", "1") != "0"              # stem conv and its weight gradient straight from a channels-last image (ops.stem_conv_*), no patch matrix
+STEM_FOLD_BN0 = os.environ.get("MC_STEM_FOLD_BN0", "1") != "0"          # linked direct stem: the BatchNorm0 backward apply inside the weight-gradient launch
 FUSE_DW_BWD = os.environ.get("MC_FUSE_DW_BWD", "1") != "0"              # stride-1 3x3 depthwise backward as one launch (ops.dwconv_bwd_fused)
 FUSE_PROJ_DGRAD = os.environ.get("MC_FUSE_PROJ_DGRAD", "1") != "0"        # projection data gradient with the SE / BatchNorm1 backward in its epilogue (ops.proj_dgrad_*)
 BN_FOLD_MIN_BYTES = int(os.environ.get("MC_BN_FOLD_MIN_BYTES", 250_000_000))
@@ -246,10 +248,13 @@ class _StemFn(torch.autograd.Function):
         l, r, t, b = mod.stem_pad
         _, oh, ow = mod.stem_geo(n, h, wd)
         c0 = w.shape[0]
-        patches = ops.stem_im2col(x, l, t, oh, ow)
         wb = ops.stem_weight_prep(w)
         training, call = mod.batch_stats, call if call is not None else _Call()
-        e, part = _conv_stats(call, ops.linear_fwd, training, patches, wb)
+        ctx.direct = STEM_DIRECT and ops.stem_direct_ok(x, c0, l, t)
+        if ctx.direct:
+            e, part = _conv_stats(call, ops.stem_conv_fwd, training, x, wb, l, t, oh, ow)
+        else:                                                      # any other layout: through the patch matrix
+            e, part = _conv_stats(call, ops.linear_fwd, training, ops.stem_im2col(x, l, t, oh, ow), wb)
         st = _bn_stats(call, part, n * oh * ow, mod._bn0, training)
         ctx.mod, ctx.st, ctx.geo, ctx.frozen = mod, st, (n, h, wd, oh, ow, c0), not training
         ctx.raw = (x.mean, x.std) if isinstance(x, ops.RawImages) else None
@@ -268,6 +273,7 @@ class _StemFn(torch.autograd.Function):
         n, h, wd, oh, ow, c0 = ctx.geo
         mod = ctx.mod
         link = ctx.link
+        fold = None
         if ctx.frozen:
             _no_fp8_frozen(mod)
         if ctx.frozen and link is not None:
@@ -279,13 +285,21 @@ class _StemFn(torch.autograd.Function):
             de, dgamma, dbeta = ops.bnact_bwd(e, n, oh * ow, c0, ctx.st, mod._bn0.weight, 1, g=dy.contiguous(), frozen=True)
         elif link is not None:
             # dy is already dZ0 = dL/d bn0(e) (block 0's data-gradient epilogue), link.part its BatchNorm-backward reductions
-            de, dgamma, dbeta = ops.bnact_bwd(e, n, oh * ow, c0, ctx.st, mod._bn0.weight, 0, g=dy.contiguous(), partials=link.part)
+            if ctx.direct and STEM_FOLD_BN0:
+                # the stem has no data gradient: de = A*dZ0 + B*e + C is only the weight gradient's operand, formed inside that launch
+                de = dy.contiguous()
+                fold, dgamma, dbeta = ops.bn_bwd_coefs(link.part, n * oh * ow, ctx.st, mod._bn0.weight)
+            else:
+                de, dgamma, dbeta = ops.bnact_bwd(e, n, oh * ow, c0, ctx.st, mod._bn0.weight, 0, g=dy.contiguous(), partials=link.part)
             link.part = None
         else:
             de, dgamma, dbeta = ops.bnact_bwd(e, n, oh * ow, c0, ctx.st, mod._bn0.weight, 1, g=dy.contiguous())
         l, r, t, b = mod.stem_pad
-        patches = ops.stem_im2col(x, l, t, oh, ow)                 # recomputed, not stored
-        dw = ops.linear_wgrad(de, patches)                         # [c0, 32]
+        if ctx.direct:
+            dw = ops.stem_conv_wgrad(de, x, l, t, oh, ow, bn=(e, fold) if fold is not None else None)     # [c0, 32]
+        else:
+            patches = ops.stem_im2col(x, l, t, oh, ow)             # recomputed, not stored
+            dw = ops.linear_wgrad(de, patches)
         if ctx.frozen and link is not None:
             dw = ops.rowscale_f32_(dw, ctx.st.scale)
         gw, gg, gb = ops.deliver_param_grads((mod._conv_stem.weight, mod._bn0.weight, mod._bn0.bias),

@@ -136,6 +136,10 @@ _SIGS = {
     "mc_image_minmax_u8": ([P, LL, LL, I, P, P], I),
     "mc_gate_weights_bf16": ([P, P, I, I, I, P, P], I),
     "mc_stem_im2col_u8": ([P, LL, LL, LL, LL, P, F, F, I, I, I, I, I, I, I, P, P], I),
+    "mc_stem_conv_blocks": ([I, I, I, I], I),
+    "mc_stem_conv_fwd": ([P, LL, LL, I, I, I, I, I, I, I, P, I, P, P, P], I),
+    "mc_stem_conv_fwd_u8": ([P, LL, LL, P, F, F, I, I, I, I, I, I, I, P, I, P, P, P], I),
+    "mc_stem_conv_wgrad": ([P, I, LL, LL, P, F, F, I, I, I, I, I, I, I, P, I, P, P, P, P, P], I),
     "mc_dwconv_stat_rows": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_bwd_data_stat_rows": ([C.POINTER(DwconvArgs)], I),
     "mc_dwconv_fwd": ([C.POINTER(DwconvArgs), P], I),

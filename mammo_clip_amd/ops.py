@@ -677,6 +677,61 @@ def stem_im2col(x, pad_l, pad_t, oh, ow):
     return out
 
 
+def stem_direct_ok(x, c0, pad_l, pad_t):
+    """can stem_conv_fwd / stem_conv_wgrad take this input?  A channels-last image (fp32, or RawImages) and a stem width the
+    kernels are built for; everything else goes through stem_im2col"""
+    d = x.data if isinstance(x, RawImages) else x
+    n, c, h, w = d.shape
+    sn, sc, sh, sw = d.stride()
+    return (c == 3 and sc == 1 and sw == 3 and (h == 1 or sh >= 3 * w) and (n == 1 or sn >= sh * (h - 1) + 3 * w)
+            and d.dtype in (torch.float32, torch.uint8) and 32 <= c0 <= 64 and c0 % 8 == 0 and 0 <= pad_l <= 2 and 0 <= pad_t <= 2)
+
+
+def _stem_src(x):
+    """(tensor, is_u8, minmax or None, mean, std) of a channels-last stem input"""
+    if isinstance(x, RawImages):
+        return x.data, 1, image_minmax_u8(x.data), x.mean, x.std
+    return x, 0, None, 0.0, 1.0
+
+
+def stem_conv_fwd(x, wb, pad_l, pad_t, oh, ow, stats=False):
+    """the stem conv without the patch matrix: e [n*oh*ow, c0] = stem_im2col(x) . wb^T, bit for bit (x: stem_direct_ok);
+    stats -> (e, [rows, 2, c0] BatchNorm statistics partials)"""
+    d, u8, mm, mean, std = _stem_src(x)
+    _chk_dev(d, wb)
+    n, _, h, w = d.shape
+    c0 = wb.shape[0]
+    e = empty((n * oh * ow, c0), BF16, d)
+    part = empty((L.load().mc_stem_conv_blocks(n, oh, ow, 1), 2, c0), torch.float32, d) if stats else None
+    _note(d.element_size() * n * h * w * 3 + 2 * n * oh * ow * c0, 2 * n * oh * ow * c0 * 27)
+    if u8:
+        L.call("mc_stem_conv_fwd_u8", _p(d), d.stride(0), d.stride(2), _p(mm), mean, std, n, h, w, pad_l, pad_t, oh, ow, _p(wb), c0,
+               _p(e), _p(part), _st())
+    else:
+        L.call("mc_stem_conv_fwd", _p(d), d.stride(0), d.stride(2), n, h, w, pad_l, pad_t, oh, ow, _p(wb), c0, _p(e), _p(part), _st())
+    return (e, part) if stats else e
+
+
+def stem_conv_wgrad(de, x, pad_l, pad_t, oh, ow, bn=None):
+    """dw [c0, 32] fp32 = de^T . stem_im2col(x) with the patches formed from the image (x: stem_direct_ok).  Per-workgroup
+    partials summed in a fixed order: no atomics, so there is nothing for set_deterministic to switch.
+    bn = (e, coef): ``de`` is dZ0 = dL/d bn0(e) and the BatchNorm0 backward apply de = coef[0]*dZ0 + coef[1]*e + coef[2]
+    (coef from bn_bwd_coefs) happens while the kernel stages dZ0 -- the apply pass of bnact_bwd and its tensor are not needed"""
+    d, u8, mm, mean, std = _stem_src(x)
+    _chk_dev(d, de)
+    n, _, h, w = d.shape
+    c0 = de.shape[1]
+    assert de.is_contiguous() and de.shape[0] == n * oh * ow
+    ws = empty((L.load().mc_stem_conv_blocks(n, oh, ow, 0 if bn is None else 2), c0, 32), torch.float32, d)
+    dw = empty((c0, 32), torch.float32, d)
+    bn_e, bn_coef = bn if bn is not None else (None, None)
+    assert bn is None or (bn_e.is_contiguous() and bn_e.shape == de.shape and bn_coef.is_contiguous() and bn_coef.shape == (3, c0))
+    _note(d.element_size() * n * h * w * 3 + 2 * n * oh * ow * c0 * (2 if bn is not None else 1), 2 * n * oh * ow * c0 * 27)
+    L.call("mc_stem_conv_wgrad", _p(d), u8, d.stride(0), d.stride(2), _p(mm), mean, std, n, h, w, pad_l, pad_t, oh, ow, _p(de), c0,
+           _p(bn_e), _p(bn_coef), _p(ws), _p(dw), _st())
+    return dw
+
+
 # ------------------------------------------------------------------------------------------- depthwise
 def _dw_args(n, h, w, c, k, stride, pad_l, pad_t, oh, ow):
     a = L.DwconvArgs()
