@@ -691,6 +691,33 @@ int mc_scale_f32(const float* x, const float* scalar_dev, float alpha, float* y,
 /* y = x / ||x||_2 per row (no epsilon) [ref: model/clip.py:90-91]; bwd: dx = (dy - y*(y.dy)) / ||x|| */
 int mc_l2norm_fwd(const float* x, int rows, int d, float* y, float* norm, void* stream);
 int mc_l2norm_bwd(const float* dy, const float* y, const float* norm, int rows, int d, float* dx, void* stream);
+/* MLP projection head [ref: model/modules/projection.py:4-20]: p = x W1^T + b1; g = GELU(p); f = g W2^T + b2;
+ * y = LayerNorm(dropout(f) + p).  The GEMMs and their gradients are mc_sgemm calls; the entry points below are the rest, fp32
+ * in both storage builds.  n = projection_dim must satisfy mc_mlp_head_supported(n): n % 8 == 0 (one Philox draw covers 8
+ * consecutive elements of a row) and 8 <= n <= mc_mlp_head_max_n() = 2048 (a wave holds a row in registers: at most four
+ * 8-float vectors per lane).  Row pointers must be 16-byte aligned. */
+int mc_mlp_head_max_n(void);
+int mc_mlp_head_supported(int n);
+/* y = x * 0.5 * (1 + erf(x / sqrt 2))  (nn.GELU's default, exact form) */
+int mc_gelu_f32_fwd(const float* x, float* y, long long count, void* stream);
+/* dx = dg * GELU'(x) + add: joins the fc branch and the residual branch into the gradient of p (dx may alias dg or add) */
+int mc_gelu_f32_bwd_add(const float* dg, const float* x, const float* add, float* dx, long long count, void* stream);
+/* one wave per row of [rows, n]: z = f * keep_scale + res, mean and (two-pass, biased) variance of z over the row,
+ * xhat = (z - mean) * rstd, y = xhat * gamma + beta; rstd = 1 / sqrt(var + eps), one float per row.  keep_scale is the
+ * factor mc_dropout_f32 applies to element row * n + col for the same (seed, stream_id): 0 or 1 / (1 - p); at p == 0 no
+ * random numbers are drawn and z = f + res.  0 <= p < 1. */
+int mc_mlp_head_ln_fwd(const float* f, const float* res, const float* gamma, const float* beta, float eps, int rows, int n,
+                       float p, unsigned long long seed, unsigned int stream_id, float* y, float* xhat, float* rstd,
+                       void* stream);
+/* LayerNorm backward per row: dz = rstd * (dy gamma - mean(dy gamma) - xhat mean(dy gamma xhat)), also the gradient of the
+ * residual; df = dz * keep_scale (the forward's mask, regenerated).  Every workgroup stores its partial column sums of
+ * dy * xhat (dgamma), dy (dbeta) and df (the fc bias gradient) to its row of ws: float[ws_rows][3][n] with
+ * ws_rows = mc_mlp_head_ln_bwd_ws_rows(rows) (the capped grid; another count is refused), every element written;
+ * mc_ordered_sum(ws, ws_rows, 3 n, 3 n, out, ...) finishes them.  No float atomics: bit-reproducible as it stands. */
+int mc_mlp_head_ln_bwd_ws_rows(int rows);
+int mc_mlp_head_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, int rows, int n, float p,
+                       unsigned long long seed, unsigned int stream_id, float* df, float* dz, float* ws, int ws_rows,
+                       void* stream);
 /* mean cross-entropy over rows of logits [rows, n], weight w; the target of row r is labels[r] + label_offset
  * (labels: int64 device array or NULL = r):
  * loss_out[0] += w * mean_r CE_r (label smoothing `smoothing`);  dlogits = w/rows * (softmax - target)  (in place)

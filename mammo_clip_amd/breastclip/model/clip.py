@@ -11,7 +11,7 @@ from torch import nn
 
 from .. import _tokens
 from ... import ops
-from .modules import load_image_encoder, load_projection_head, load_text_encoder
+from .modules import MLPProjectionHead, load_image_encoder, load_projection_head, load_text_encoder
 
 log = logging.getLogger(__name__)
 
@@ -266,17 +266,30 @@ class BreastClip(nn.Module):
             txt2 = self.encode_text(self._tokens_to_device(batch["text_tokens2"], device))
         return txt, txt2
 
+    def _project(self, head, x, role):
+        """one projection-head call.  The MLP head's dropout mask is seeded by the call counter of the encoder that produced
+        ``x`` (read after that encoder ran, so a re-forward from rewound counters -- engine micro-batching -- draws the same
+        mask) and a stream id per role (0 image, 1 text, 2 second text, 3 second view): four masks per forward."""
+        if not isinstance(head, MLPProjectionHead):
+            return head(x)
+        if role in (0, 3):
+            counter = getattr(getattr(self.image_encoder, "rng", None), "calls", None)
+        else:
+            te = getattr(self.text_encoder, "text_encoder", self.text_encoder)
+            counter = getattr(te, "_calls", None)
+        return head(x, seed=counter, stream_id=role)
+
     def _finish(self, batch, device, img, txt, txt2, two, view=None):
-        img_e = self.image_projection(img) if self.projection else img
-        txt_e = self.text_projection(txt) if self.projection else txt
+        img_e = self._project(self.image_projection, img, 0) if self.projection else img
+        txt_e = self._project(self.text_projection, txt, 1) if self.projection else txt
         img_e, txt_e = _L2NormFn.apply(img_e), _L2NormFn.apply(txt_e)
         out = {"image_embeddings": img_e, "text_embeddings": txt_e,
                "labels": torch.arange(img_e.shape[0], device=device), "logit_scale": self.logit_scale.exp()}
         if two:
-            txt2_e = self.text_projection(txt2) if self.projection else txt      # [ref quirk: clip.py:105]
+            txt2_e = self._project(self.text_projection, txt2, 2) if self.projection else txt      # [ref quirk: clip.py:105]
             out["text_embeddings2"] = _L2NormFn.apply(txt2_e)
             if view is None:
                 view = self.encode_image(batch["image_views"].to(device))
-            view_e = self.image_projection(view) if self.projection else view
+            view_e = self._project(self.image_projection, view, 3) if self.projection else view
             out["image_view_embeddings"] = _L2NormFn.apply(view_e)
         return out

@@ -21,6 +21,7 @@ on its own and usable outside the model:
     torch.ops.mammoclip.dwconv(x, w_kkc, n, h, w, k, stride, pad_l, pad_t, oh, ow)   depthwise conv, differentiable
     torch.ops.mammoclip.linear_dgrad / linear_wgrad / dwconv_bwd_data / dwconv_bwd_weight      the explicit backward ops
     torch.ops.mammoclip.gelu / gelu_bwd / softmax / l2norm / cross_entropy_ (in place)         pointwise / row kernels
+    torch.ops.mammoclip.gelu_f32 / gelu_f32_bwd_add / mlp_head_ln / mlp_head_ln_bwd             the MLP projection head's (fp32)
 
 Every operator has a fake (meta) implementation, so ``torch.library.opcheck`` and tracing work without a GPU; the real
 implementations exist for device type "cuda" only -- a CPU tensor raises (there is no fallback).
@@ -185,6 +186,50 @@ def _(x):
     return torch.empty_like(x), x.new_empty((x.shape[0],))
 
 
+@_op("gelu_f32")
+def gelu_f32(x: Tensor) -> Tensor:
+    return ops.gelu_f32_fwd(x)
+
+
+@gelu_f32.register_fake
+def _(x):
+    return torch.empty_like(x)
+
+
+@_op("gelu_f32_bwd_add")
+def gelu_f32_bwd_add(dg: Tensor, x: Tensor, add: Tensor) -> Tensor:
+    return ops.gelu_f32_bwd_add(dg, x, add)
+
+
+@gelu_f32_bwd_add.register_fake
+def _(dg, x, add):
+    return torch.empty_like(x)
+
+
+@_op("mlp_head_ln")
+def mlp_head_ln(f: Tensor, res: Tensor, gamma: Tensor, beta: Tensor, eps: float, p: float, seed: int,
+                stream_id: int) -> Tuple[Tensor, Tensor, Tensor]:
+    return ops.mlp_head_ln_fwd(f, res, gamma, beta, eps, p, seed, stream_id)
+
+
+@mlp_head_ln.register_fake
+def _(f, res, gamma, beta, eps, p, seed, stream_id):
+    return torch.empty_like(f), torch.empty_like(f), f.new_empty((f.shape[0],))
+
+
+@_op("mlp_head_ln_bwd")
+def mlp_head_ln_bwd(dy: Tensor, xhat: Tensor, rstd: Tensor, gamma: Tensor, p: float, seed: int,
+                    stream_id: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return ops.mlp_head_ln_bwd(dy, xhat, rstd, gamma, p, seed, stream_id)
+
+
+@mlp_head_ln_bwd.register_fake
+def _(dy, xhat, rstd, gamma, p, seed, stream_id):
+    n = xhat.shape[1]
+    return (torch.empty_like(xhat), torch.empty_like(xhat), xhat.new_empty((n,)), xhat.new_empty((n,)),
+            xhat.new_empty((n,)))
+
+
 @_op("cross_entropy_", mutates=("logits", "loss"))
 def cross_entropy_(logits: Tensor, loss: Tensor, label_offset: int, weight: float, smoothing: float,
                    labels: Optional[Tensor] = None) -> None:
@@ -263,6 +308,7 @@ for _name, (_schema, _impl, _meta) in _MODEL_OPS.items():
     _lib.impl(_name, _meta, "Meta")
 
 OPS = ("linear", "linear_dgrad", "linear_wgrad", "dwconv", "dwconv_bwd_data", "dwconv_bwd_weight", "gelu", "gelu_bwd",
-       "softmax", "l2norm", "cross_entropy_") + tuple(_MODEL_OPS)
+       "softmax", "l2norm", "gelu_f32", "gelu_f32_bwd_add", "mlp_head_ln", "mlp_head_ln_bwd", "cross_entropy_") \
+    + tuple(_MODEL_OPS)
 
 ops._bind_model_ops()      # ops' wrappers resolve the overloads once (either module may be imported first)

@@ -234,6 +234,13 @@ _SIGS = {
     "mc_scale_f32": ([P, P, F, P, LL, P], I),
     "mc_l2norm_fwd": ([P, I, I, P, P, P], I),
     "mc_l2norm_bwd": ([P, P, P, I, I, P, P], I),
+    "mc_mlp_head_max_n": ([], I),
+    "mc_mlp_head_supported": ([I], I),
+    "mc_gelu_f32_fwd": ([P, P, LL, P], I),
+    "mc_gelu_f32_bwd_add": ([P, P, P, P, LL, P], I),
+    "mc_mlp_head_ln_fwd": ([P, P, P, P, F, I, I, F, ULL, U, P, P, P, P], I),
+    "mc_mlp_head_ln_bwd_ws_rows": ([I], I),
+    "mc_mlp_head_ln_bwd": ([P, P, P, P, I, I, F, ULL, U, P, P, P, I, P], I),
     "mc_ce_fwd_bwd": ([P, I, I, P, I, F, F, P, P, P], I),
     "mc_sim_rank": ([P, P, P, P, I, I, I, P], I),
     "mc_sim_topk_ws_bytes": ([I, I, I], LL),

@@ -1568,6 +1568,61 @@ def l2norm_bwd(dy, y, norm):
     return dx
 
 
+def mlp_head_max_n():
+    return int(L.load().mc_mlp_head_max_n())
+
+
+def mlp_head_supported(n):
+    return bool(L.load().mc_mlp_head_supported(int(n)))
+
+
+def gelu_f32_fwd(x):
+    """exact-erf GELU of a contiguous fp32 tensor (the MLP projection head's activation)"""
+    _chk_dev(x)
+    y = torch.empty_like(x)
+    L.call("mc_gelu_f32_fwd", _p(x), _p(y), x.numel(), _st())
+    return y
+
+
+def gelu_f32_bwd_add(dg, x, add):
+    """dg * GELU'(x) + add, contiguous fp32 tensors of one shape"""
+    _chk_dev(dg, x, add)
+    dx = torch.empty_like(x)
+    L.call("mc_gelu_f32_bwd_add", _p(dg), _p(x), _p(add), _p(dx), x.numel(), _st())
+    return dx
+
+
+def mlp_head_ln_fwd(f, res, gamma, beta, eps, p, seed, stream_id):
+    """(y, xhat, rstd) of LayerNorm(dropout(f) + res) over the rows of contiguous fp32 [rows, n] tensors; the dropout mask is
+    dropout_f32's for the same (seed, stream_id) and is not stored"""
+    _chk_dev(f, res, gamma, beta)
+    rows, n = f.shape
+    y, xhat = torch.empty_like(f), torch.empty_like(f)
+    rstd = empty((rows,), torch.float32, f)
+    L.call("mc_mlp_head_ln_fwd", _p(f), _p(res), _p(gamma), _p(beta), float(eps), rows, n, float(p), int(seed),
+           int(stream_id), _p(y), _p(xhat), _p(rstd), _st())
+    return y, xhat, rstd
+
+
+def mlp_head_ln_bwd(dy, xhat, rstd, gamma, p, seed, stream_id):
+    """(df, dz, dgamma, dbeta, dbias) of mlp_head_ln_fwd: dz is the gradient of the pre-LayerNorm sum (and of ``res``), df of
+    ``f``; the three [n] vectors are the column sums of dy * xhat, dy and df -- per-workgroup partials summed in a fixed order:
+    no atomics, so there is nothing for set_deterministic to switch.  Five own tensors (parameter gradients are not views)."""
+    _chk_dev(dy, xhat, rstd, gamma)
+    rows, n = xhat.shape
+    df, dz = torch.empty_like(xhat), torch.empty_like(xhat)
+    ws_rows = int(L.load().mc_mlp_head_ln_bwd_ws_rows(rows))
+    ws = empty((ws_rows, 3, n), torch.float32, xhat)
+    L.call("mc_mlp_head_ln_bwd", _p(dy), _p(xhat), _p(rstd), _p(gamma), rows, n, float(p), int(seed), int(stream_id),
+           _p(df), _p(dz), _p(ws), ws_rows, _st())
+    sums = []
+    for i in range(3):
+        out = empty((n,), torch.float32, xhat)
+        L.call("mc_ordered_sum", _p(ws) + 4 * n * i, ws_rows, 3 * n, n, _p(out), 0, _st())
+        sums.append(out)
+    return df, dz, sums[0], sums[1], sums[2]
+
+
 def ce_fwd_bwd(logits, label_offset, w, loss_out, smoothing=0.0, labels=None):
     rows, n = logits.shape
     row_ws = empty((rows,), torch.float32, logits)
