@@ -749,6 +749,35 @@ int mc_sim_softmax(const float* a, const float* b, float* p, int N, int M, int D
  * AUROC = (counts[0] + 0.5 counts[1]) / (counts[2] counts[3]), the Mann-Whitney form of roc_curve + auc
  * [ref: evaluator.py:176-177,180-181,188-189] */
 int mc_auroc_counts(const float* score, const int* label, long long* counts, int N, void* stream);
+/* Binary-classification metrics of one finding without a sort.  score fp32 [N], label int32 [N]
+ * (0 or 1; the kernels take label != 0 as positive and COUNT the others in the record), 1 <= N <= 2^24: counts fit 32 bits and
+ * count products fit 64-bit integers and fp64 exactly.  No float atomics anywhere: integer atomics for the counts, fp64 sums
+ * as per-workgroup partials added in a fixed order (the mc_ordered_sum pattern), so two calls return the same bits.
+ *
+ * counts [N][5], per sample i: positives / negatives j with s_j >= s_i (i included) = (TP, FP) at threshold s_i; the same
+ * with s_j > s_i = (TP, FP) at the next higher distinct threshold, (0, 0) at the curve's start; #{j < i : s_j == s_i}, which
+ * is 0 for exactly one sample per distinct score (the representative of that threshold).  All pairs are compared from LDS
+ * tiles of 2048 partners, like mc_auroc_counts.
+ * [ref: evaluator.py:301-309 (pfbeta_binarized: one pass over the samples per positive), 340-346 (precision_recall_curve)] */
+int mc_rank_counts(const float* score, const int* label, unsigned int* counts, int N, void* stream);
+/* record: 20 eight-byte slots.  Integers [0..16): n_pos, n_neg; the AUROC pair counts gt = sum_pos (n_neg - neg_ge) and
+ * eq = sum_pos (neg_ge - neg_gt); tp, fp and the score (fp32 bits in the low word) of the best-pF1 threshold among the
+ * positives' scores -- 2 tp / (tp + fp + n_pos) compared exactly as a cross product, the higher threshold on equal value,
+ * (0, 0, -inf) without a positive; tp, fp, tn, fn at `threshold` with (double) score >= threshold predicted positive; the
+ * number K of distinct scores; the number of NaN scores; the number of labels outside {0, 1}; two spare slots (0).
+ * fp64 [16..20): PR-AUC = sum over representatives of (R1 - R0)(P1 + P0)/2 and average precision = sum of (R1 - R0) P1
+ * (P = tp/(tp+fp), R = tp/n_pos, P0 = 1 at the start point; NaN without a positive); sum of clip(s, 0, 1) over the positives
+ * and over the negatives.  counts == NULL: only the fields that need no counts (n_pos, n_neg, the threshold's four, NaN and
+ * label counts, clip sums); the others are 0 / NaN.  ws: mc_cls_record_ws_bytes(N) bytes (0 for N out of range).
+ * [ref: evaluator.py:301-346 (pfbeta_binarized, auroc, pfbeta, pr_auc); Classifiers/experiments.py:58,66-69 (pred >= 0.5)] */
+long long mc_cls_record_ws_bytes(int N);
+int mc_cls_record(const float* score, const int* label, const unsigned int* counts, int N, double threshold, long long* record,
+                  void* ws, void* stream);
+/* the integer PR / ROC curve: tp[k], fp[k], threshold[k] of the k-th distinct score in ascending order, K = the record's
+ * number of distinct scores (an entry whose position is >= K is not written); pos_ws: N words of scratch
+ * [ref: evaluator.py:341-344 (pr_auc(get_all=True): precision = tp/(tp+fp), recall = tp/n_pos, finished by the caller)] */
+int mc_cls_curve(const float* score, const unsigned int* counts, int N, int K, unsigned int* pos_ws, int* tp, int* fp,
+                 float* threshold, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * training augmentation (augment.hip): flips, affine and elastic warp of the reference's train transform as one gather per

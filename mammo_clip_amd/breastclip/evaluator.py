@@ -4,10 +4,14 @@
 (evaluator.py:173).  ``retrieval_i2t`` / ``retrieve`` / ``zeroshot_metrics`` are the numbers a checkpoint is judged on
 (eval_img_text_retrieval, eval_zeroshot): on device tensors they run the streamed similarity kernels of csrc/retrieval.hip
 -- the N x M similarity matrix is never stored and nothing but the final scalars leaves the device -- on numpy arrays plain
-numpy on the host.  No sklearn / scipy anywhere.
+numpy on the host.  The module-level ``pfbeta`` / ``pfbeta_binarized`` / ``auroc`` / ``pr_auc`` / ``binary_metrics`` /
+``classification_score`` / ``multiclass_classification`` [ref: evaluator.py:255-346] follow the same rule: device tensors go
+through the rank-count kernels of csrc/retrieval.hip and one small record is read back, numpy arrays through a sort on the
+host.  No sklearn / scipy anywhere.
 
-Out of scope: tokenising prompts, datasets and loaders, ``classification_score`` and the pF1 helpers
-(evaluator.py:255-346), sharding one evaluation over several ranks, and any change to ``engine.validate``."""
+Out of scope: tokenising prompts, datasets and loaders, bootstrap confidence intervals, sharding one evaluation over several
+ranks, and any change to ``engine.validate``."""
+import logging
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -15,6 +19,8 @@ import torch
 
 from . import _tokens
 from .model import build_model
+
+log = logging.getLogger(__name__)
 
 
 class Evaluator:
@@ -131,14 +137,16 @@ class Evaluator:
         return np.take_along_axis(s, idx, axis=1), idx.astype(np.int32)
 
     @staticmethod
-    def zeroshot_metrics(image_embeddings, prompt_embeddings: Dict, labels: Dict) -> Dict:
+    def zeroshot_metrics(image_embeddings, prompt_embeddings: Dict, labels: Dict, detail: bool = False) -> Dict:
         """Zero-shot classification [ref: evaluator.py:160-190]: ``prompt_embeddings`` = ``{label_text: [M, D]}`` (the encoded
         prompts of one finding), ``labels`` = ``{"mass", "calc", "density", "cancer"}`` (whichever are present, one integer per
         image).  ``mass`` / ``suspicious_calcification`` / ``cancer`` / ``malignancy``: AUROC of the softmax's column 1
         against ``mass`` / ``calc`` / ``cancer`` / ``cancer``; ``density``: accuracy of the argmax.  Other keys are skipped, as
         the reference does.  AUROC is the Mann-Whitney form (pairs won + half the pairs tied) / (positives x negatives) of
         roc_curve + auc; with one class only it is NaN.  Device tensors (unit-norm fp32 rows, as in ``retrieval_i2t``):
-        ``mc_sim_softmax`` + ``mc_auroc_counts``."""
+        ``mc_sim_softmax`` + ``mc_auroc_counts``.  ``detail=True``: every binary finding maps to its ``binary_metrics``
+        dict (threshold 0.5) instead of the bare AUROC -- on the device ``mc_rank_counts`` + ``mc_cls_record``, one record read
+        per finding."""
         source = {"suspicious_calcification": "calc", "mass": "mass", "density": "density", "cancer": "cancer",
                   "malignancy": "cancer"}
         dev = _on_device(image_embeddings)
@@ -161,6 +169,9 @@ class Evaluator:
                 y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(a.device)
                 if key == "density":
                     pending.append((label_text, None, (p.argmax(dim=1) == y).sum()))
+                elif detail:
+                    col, y = _dev_score_label(y, p[:, 1])
+                    pending.append((label_text, ops.cls_record(col, y, ops.rank_counts(col, y)), None))
                 else:
                     pending.append((label_text, ops.auroc_counts(p[:, 1].contiguous(), y), None))
             else:
@@ -170,6 +181,8 @@ class Evaluator:
                 y = np.asarray(y)
                 if key == "density":
                     results[label_text] = float((p.argmax(axis=1) == y).sum()) / len(y)
+                elif detail:
+                    results[label_text] = binary_metrics(y, p[:, 1])
                 else:
                     pos, neg = p[y != 0, 1], np.sort(p[y == 0, 1])
                     lo, hi = np.searchsorted(neg, pos, side="left"), np.searchsorted(neg, pos, side="right")
@@ -179,6 +192,8 @@ class Evaluator:
         for label_text, counts, correct in pending:                           # one host read per finding, after all launches
             if counts is None:
                 results[label_text] = int(correct) / a.shape[0]
+            elif detail:
+                results[label_text] = _metrics_of_record(_read_record(counts))
             else:
                 results[label_text] = _auroc(*[int(v) for v in counts.cpu()])
         return results
@@ -186,6 +201,239 @@ class Evaluator:
 
 def _auroc(gt: int, eq: int, npos: int, nneg: int) -> float:
     return (gt + 0.5 * eq) / (npos * nneg) if npos and nneg else float("nan")
+
+
+# ------------------------------------------------------------------------------- binary-classification metrics of one finding
+# [ref: evaluator.py:255-346].  Everything is finished from exact integers: (TP, FP) at every distinct threshold.  On device
+# tensors they come from the all-pairs rank counts of csrc/retrieval.hip; on numpy arrays from a sort and
+# searchsorted in fp64.  A NaN score or a label outside {0, 1} raises ValueError on both paths.
+BINARY_KEYS = ("AUROC", "pF", "prauc", "F1", "Accuracy", "ACC_POSITIVES", "AP")
+_NAN = float("nan")
+
+
+def pfbeta(gt, pred, beta) -> float:
+    """Probabilistic F-beta on scores clipped to [0, 1] [ref: evaluator.py:316-337]: ctp / cfp are the sums of the clipped
+    scores over positives / negatives.  0.0 when ctp + cfp == 0 or precision or recall is 0; NaN without a positive (the
+    reference divides by zero there)."""
+    if _on_device(pred):
+        from .. import ops
+        score, label = _dev_score_label(gt, pred)
+        rec = _read_record(ops.cls_record(score, label, None))
+        n_pos, ctp, cfp = rec["n_pos"], rec["clip_pos"], rec["clip_neg"]
+    else:
+        y, s = _host_score_label(gt, pred)
+        c = np.clip(s, 0.0, 1.0)
+        n_pos, ctp, cfp = int(y.sum()), float(c[y].sum()), float(c[~y].sum())
+    if n_pos == 0:
+        return _NAN
+    if ctp + cfp == 0:
+        return 0.0
+    b2 = beta * beta
+    p, r = ctp / (ctp + cfp), ctp / n_pos
+    return (1 + b2) * (p * r) / (b2 * p + r) if p > 0 and r > 0 else 0.0
+
+
+def pfbeta_binarized(gt, pred) -> float:
+    """The best pF1 of ``pred >= th`` over the thresholds ``th`` taken from the positives' scores [ref: evaluator.py:301-309,
+    without its positives x samples loop]; NaN without a positive (the reference raises on ``max([])``)."""
+    if _on_device(pred):
+        from .. import ops
+        score, label = _dev_score_label(gt, pred)
+        rec = _read_record(ops.cls_record(score, label, ops.rank_counts(score, label)))
+        return _pf1(rec["best_tp"], rec["best_fp"], rec["n_pos"])
+    y, s = _host_score_label(gt, pred)
+    return _host_best_pf1(y, s)
+
+
+def auroc(gt, pred) -> float:
+    """roc_auc_score in its Mann-Whitney form (pairs won + half the pairs tied) / (positives x negatives)
+    [ref: evaluator.py:312-313]; NaN with one class only"""
+    if _on_device(pred):
+        from .. import ops
+        score, label = _dev_score_label(gt, pred)
+        rec = _read_record(ops.cls_record(score, label, ops.rank_counts(score, label)))
+        return _auroc(rec["gt"], rec["eq"], rec["n_pos"], rec["n_neg"])
+    y, s = _host_score_label(gt, pred)
+    return _host_auroc(y, s)
+
+
+def pr_auc(gt, pred, get_all=False):
+    """The trapezoid under sklearn's precision_recall_curve [ref: evaluator.py:340-346].  ``get_all=True``:
+    ``(score, precision, recall)`` in sklearn's layout -- every distinct threshold ascending, then the closing point
+    (precision 1, recall 0): K + 1 entries, no cut at full recall.  Device tensors: the score is the record's fp64 sum, the
+    arrays are ``tp / (tp + fp)`` and ``tp / n_pos`` of the integer curve, finished on the host.  NaN without a positive."""
+    if _on_device(pred):
+        from .. import ops
+        score, label = _dev_score_label(gt, pred)
+        counts = ops.rank_counts(score, label)
+        rec = _read_record(ops.cls_record(score, label, counts))
+        if not get_all:
+            return rec["prauc"]
+        tp, fp, _ = ops.cls_curve(score, counts, rec["k"])
+        precision, recall = _curve_arrays(tp.cpu().numpy(), fp.cpu().numpy(), rec["n_pos"])
+        return rec["prauc"], precision, recall
+    y, s = _host_score_label(gt, pred)
+    tp, fp, _ = _host_curve(y, s)
+    precision, recall = _curve_arrays(tp, fp, int(y.sum()))
+    area = _trapezoid(precision, recall) if y.any() else _NAN
+    return (area, precision, recall) if get_all else area
+
+
+def binary_metrics(gt, pred, threshold=0.5) -> Dict:
+    """One finding's dict with the keys ``classification_score`` consumes plus ``"AP"``: ``AUROC``, ``pF``
+    (= ``pfbeta_binarized``), ``prauc``, then ``F1``, ``Accuracy`` and ``ACC_POSITIVES`` (the share of positives predicted
+    positive [ref: Classifiers/experiments.py:66-69]) at ``pred >= threshold``, and the average precision ``AP``.  Device
+    tensors: one counts pass, one reduction, and one read of the 20-slot record -- no per-sample data leaves the device."""
+    if _on_device(pred):
+        from .. import ops
+        score, label = _dev_score_label(gt, pred)
+        return _metrics_of_record(_read_record(ops.cls_record(score, label, ops.rank_counts(score, label), threshold)))
+    y, s = _host_score_label(gt, pred)
+    tp, fp, _ = _host_curve(y, s)
+    n_pos, n_neg = int(y.sum()), int((~y).sum())
+    precision, recall = _curve_arrays(tp, fp, n_pos)
+    hit = s >= threshold
+    ctp, cfp = int((hit & y).sum()), int((hit & ~y).sum())
+    return _finish_metrics(_host_auroc(y, s), _host_best_pf1(y, s), _trapezoid(precision, recall) if n_pos else _NAN,
+                           -float(np.sum(np.diff(recall) * precision[:-1])) if n_pos else _NAN,
+                           ctp, cfp, n_neg - cfp, n_pos - ctp)
+
+
+def classification_score(result: Dict) -> Dict:
+    """Averages the per-finding dicts of ``result`` (``{finding: binary_metrics(...)}``) into the reference's ``"...(Avg)"``
+    keys, adds them to ``result`` and returns it [ref: evaluator.py:255-277]"""
+    findings = list(result.values())
+    for value in findings:
+        for k, v in value.items():
+            if isinstance(v, np.floating):
+                value[k] = float(v)
+    for key, name in (("ACC_POSITIVES", "ACC_POSITIVES(Avg)"), ("pF", "pF(Avg)"), ("prauc", "prauc(Avg)"),
+                      ("AUROC", "AUROC(Avg)"), ("F1", "F1(Avg)"), ("Accuracy", "Accuracy(Avg)")):
+        result[name] = np.mean([value[key] for value in findings])
+    log.info("\n".join(f"{k}: {v}" for k, v in result.items()))
+    return result
+
+
+def multiclass_classification(preds, labels, class_list: Sequence) -> Dict:
+    """Per-class accuracy of the argmax over one-hot ``labels`` [N, C], then ``Accuracy(Macro)`` and ``Accuracy(Micro)``
+    [ref: evaluator.py:280-298].  Device tensors: torch integer ops, one read of the 2 C counts."""
+    c = len(class_list)
+    if _on_device(preds):
+        lab = torch.as_tensor(labels).to(preds.device)
+        hit = preds.argmax(dim=1)[:, None] == torch.arange(c, device=preds.device)[None, :]
+        lab = lab[:, :c].to(torch.int64)
+        both = torch.stack([(lab * hit).sum(dim=0), lab.sum(dim=0)]).cpu().numpy()
+        correct, total, n = both[0], both[1], lab.shape[0]
+    else:
+        preds, lab = np.asarray(preds), np.asarray(labels)
+        arg = np.argmax(preds, axis=1)
+        total = np.asarray([lab[:, i].sum() for i in range(c)])
+        correct = np.asarray([(lab[:, i] * (arg == i)).sum() for i in range(c)])
+        n = len(lab)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        result = {name: float(np.float64(correct[i]) / np.float64(total[i])) for i, name in enumerate(class_list)}
+    result["Accuracy(Macro)"] = float(np.mean(list(result.values())))
+    result["Accuracy(Micro)"] = float(correct.sum()) / n
+    log.info(" / ".join(f"{k}: {v:.3f}" for k, v in result.items()))
+    return result
+
+
+def _pf1(tp: int, fp: int, n_pos: int) -> float:
+    """pfbeta(gt, binarized, 1) of the reference on integer counts: c_precision = tp / (tp + fp), c_recall = tp / n_pos"""
+    if n_pos == 0:
+        return _NAN
+    if tp == 0:
+        return 0.0
+    p, r = tp / (tp + fp), tp / n_pos
+    return 2 * (p * r) / (p + r)
+
+
+def _finish_metrics(auc_roc, pf, prauc, ap, tp, fp, tn, fn) -> Dict:
+    return {"AUROC": auc_roc, "pF": pf, "prauc": prauc,
+            "F1": 2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0,       # sklearn's f1_score (0 when undefined)
+            "Accuracy": (tp + tn) / (tp + fp + tn + fn),
+            "ACC_POSITIVES": tp / (tp + fn) if tp + fn else _NAN,
+            "AP": ap}
+
+
+def _metrics_of_record(rec: Dict) -> Dict:
+    return _finish_metrics(_auroc(rec["gt"], rec["eq"], rec["n_pos"], rec["n_neg"]),
+                           _pf1(rec["best_tp"], rec["best_fp"], rec["n_pos"]), rec["prauc"], rec["ap"],
+                           rec["tp"], rec["fp"], rec["tn"], rec["fn"])
+
+
+def _read_record(record) -> Dict:
+    """the one host read of a device record (ops.cls_record); raises for what the device counted as unusable input"""
+    from .. import ops
+    raw = record.cpu().numpy()
+    rec = {k: int(v) for k, v in zip(ops.CLS_RECORD_INTS, raw)}
+    rec.update({k: float(v) for k, v in zip(ops.CLS_RECORD_F64, raw[16:].view(np.float64))})
+    rec["best_threshold"] = float(np.array([raw[6] & 0xffffffff], dtype=np.uint32).view(np.float32)[0])
+    _raise_bad_input(rec["n_nan"], rec["n_bad_label"])
+    return rec
+
+
+def _raise_bad_input(n_nan: int, n_bad_label: int):
+    if n_nan:
+        raise ValueError(f"{n_nan} scores are NaN")
+    if n_bad_label:
+        raise ValueError(f"{n_bad_label} labels are outside {{0, 1}}")
+
+
+def _dev_score_label(gt, pred):
+    """fp32 contiguous [N] scores and int32 [N] labels on pred's device; a label that is not 0 or 1 (in any dtype) becomes 2,
+    which the kernels count -- nothing is read back here"""
+    score = pred.reshape(-1).to(torch.float32).contiguous()
+    y = torch.as_tensor(np.asarray(gt) if not torch.is_tensor(gt) else gt).to(score.device).reshape(-1)
+    if y.numel() != score.numel() or score.numel() == 0:
+        raise ValueError("one label per score, and at least one score")
+    if y.dtype != torch.int32:
+        y = torch.where((y == 0) | (y == 1), y.to(torch.int32), torch.full_like(y, 2, dtype=torch.int32))
+    return score, y.contiguous()
+
+
+def _host_score_label(gt, pred):
+    """(bool [N] positives, fp64 [N] scores)"""
+    y = np.asarray(gt.cpu() if torch.is_tensor(gt) else gt).reshape(-1)
+    s = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred, dtype=np.float64).reshape(-1)
+    if len(y) != len(s) or len(s) == 0:
+        raise ValueError("one label per score, and at least one score")
+    _raise_bad_input(int(np.isnan(s).sum()), int(((y != 0) & (y != 1)).sum()))
+    return y != 0, s
+
+
+def _host_curve(y, s):
+    """(tp [K], fp [K], threshold [K]): positives / negatives with score >= each distinct score, ascending"""
+    pos, neg, thr = np.sort(s[y]), np.sort(s[~y]), np.unique(s)
+    return len(pos) - np.searchsorted(pos, thr, side="left"), len(neg) - np.searchsorted(neg, thr, side="left"), thr
+
+
+def _curve_arrays(tp, fp, n_pos: int):
+    """sklearn's (precision, recall) from the integer curve plus the closing point (1, 0)"""
+    tp = tp.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision, recall = tp / (tp + fp), tp / np.float64(n_pos)
+    return np.append(precision, 1.0), np.append(recall, 0.0)
+
+
+def _trapezoid(precision, recall) -> float:
+    return -float(np.sum(np.diff(recall) * (precision[1:] + precision[:-1]) / 2.0))
+
+
+def _host_auroc(y, s) -> float:
+    pos, neg = s[y], np.sort(s[~y])
+    lo, hi = np.searchsorted(neg, pos, side="left"), np.searchsorted(neg, pos, side="right")
+    return _auroc(int(lo.sum()), int((hi - lo).sum()), len(pos), len(neg))
+
+
+def _host_best_pf1(y, s) -> float:
+    if not y.any():
+        return _NAN
+    pos, neg = np.sort(s[y]), np.sort(s[~y])
+    thr = np.unique(pos)
+    tp, fp = len(pos) - np.searchsorted(pos, thr, side="left"), len(neg) - np.searchsorted(neg, thr, side="left")
+    p, r = tp / (tp + fp), tp / len(pos)
+    return float(np.max(2 * (p * r) / (p + r)))
 
 
 def _on_device(x) -> bool:

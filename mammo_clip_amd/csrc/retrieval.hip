@@ -1,6 +1,7 @@
 // Evaluation metrics on the device: image-to-report retrieval ranks, top-k retrieval, the zero-shot softmax and the pair
-// counts behind AUROC.  All fp32 (embeddings are fp32 in both storage builds).
-// [ref: breastclip/evaluator.py:146-252 (eval_zeroshot, eval_img_text_retrieval)]
+// counts behind AUROC; per-sample rank counts and the record of binary-classification metrics (pF1, PR-AUC, AP, threshold
+// scores) reduced from them.  All fp32 (embeddings are fp32 in both storage builds).
+// [ref: breastclip/evaluator.py:146-252 (eval_zeroshot, eval_img_text_retrieval), 255-346 (classification scores)]
 //
 // The similarity product a[N,D] . b[M,D]^T is STREAMED: a workgroup owns 64 image rows and a chunk of the M texts, walks the
 // chunk in tiles of 128 texts staged through LDS, and reduces every 64 x 128 tile of scores to what the caller wants (a count
@@ -285,6 +286,285 @@ __global__ __launch_bounds__(256) void auroc_counts_k(const float* __restrict__ 
     if (threadIdx.x < 4 && s_red[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_red[threadIdx.x]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Binary-classification metrics (pF1, PR-AUC, AP, threshold scores) from per-sample rank counts: the same all-pairs sweep as
+// auroc_counts_k gives every point of the ROC and PR curves as exact integers, without a sort.
+constexpr int RC_I = 256;       // samples of one workgroup (one per thread)
+constexpr int RC_J = 2048;      // comparison partners of one workgroup
+constexpr int RC_COLS = 5;      // pos_ge, neg_ge, pos_gt, neg_gt, earlier_eq
+
+// counts[i][0..3] += positives / negatives j of the tile with s_j >= s_i, then with s_j > s_i (i itself is a partner);
+// counts[i][4] += #{j < i in the tile : s_j == s_i}.  A NaN score compares false both ways and counts nowhere.
+__global__ __launch_bounds__(RC_I) void rank_counts_k(const float* __restrict__ score, const int* __restrict__ label,
+                                                      uint32_t* __restrict__ counts, int N) {
+    __shared__ float s_s[RC_J];
+    __shared__ int s_pos[RC_J];
+    const int i = blockIdx.x * RC_I + threadIdx.x;
+    const int j0 = blockIdx.y * RC_J, jn = min(RC_J, N - j0);
+    for (int e = threadIdx.x; e < jn; e += RC_I) {
+        s_s[e] = score[j0 + e];
+        s_pos[e] = label[j0 + e] != 0 ? 1 : 0;
+    }
+    __syncthreads();
+    if (i >= N) return;
+    const float si = score[i];
+    int ge = 0, gt = 0, pge = 0, pgt = 0, early = 0;
+    const int ne = min(jn, i - j0);                             // partners [0, ne) of the tile come before i (ne may be <= 0)
+    for (int e = 0; e < jn; ++e) {
+        const float sj = s_s[e];
+        const int p = s_pos[e];
+        const int a = (int)(sj >= si), b = (int)(sj > si);
+        ge += a;
+        gt += b;
+        pge += a & p;
+        pgt += b & p;
+        early += (int)(e < ne) & (a ^ b);                       // s_j == s_i  <=>  >= and not >
+    }
+    uint32_t* c = counts + (long long)i * RC_COLS;
+    // integer adds: the result does not depend on the order in which the partner tiles' workgroups finish
+    if (pge) atomicAdd(c + 0, (uint32_t)pge);
+    if (ge - pge) atomicAdd(c + 1, (uint32_t)(ge - pge));
+    if (pgt) atomicAdd(c + 2, (uint32_t)pgt);
+    if (gt - pgt) atomicAdd(c + 3, (uint32_t)(gt - pgt));
+    if (early) atomicAdd(c + 4, (uint32_t)early);
+}
+
+// pos[i] += #{representatives j of the tile : s_j < s_i} for every representative i (earlier_eq == 0: the first sample of its
+// distinct score): the index of i's threshold among the distinct thresholds in ascending order
+__global__ __launch_bounds__(RC_I) void rep_rank_k(const float* __restrict__ score, const uint32_t* __restrict__ counts,
+                                                   uint32_t* __restrict__ pos, int N) {
+    __shared__ float s_s[RC_J];
+    const float nan = __uint_as_float(0x7fc00000u);
+    const int i = blockIdx.x * RC_I + threadIdx.x;
+    const int j0 = blockIdx.y * RC_J, jn = min(RC_J, N - j0);
+    for (int e = threadIdx.x; e < jn; e += RC_I) s_s[e] = counts[(long long)(j0 + e) * RC_COLS + 4] == 0 ? score[j0 + e] : nan;
+    __syncthreads();
+    if (i >= N || counts[(long long)i * RC_COLS + 4] != 0) return;
+    const float si = score[i];
+    int lt = 0;
+    for (int e = 0; e < jn; ++e) lt += (int)(s_s[e] < si);
+    if (lt) atomicAdd(pos + i, (uint32_t)lt);
+}
+__global__ void curve_scatter_k(const float* __restrict__ score, const uint32_t* __restrict__ counts,
+                                const uint32_t* __restrict__ pos, int N, int K, int* __restrict__ tp, int* __restrict__ fp,
+                                float* __restrict__ thr) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N || counts[(long long)i * RC_COLS + 4] != 0) return;
+    const uint32_t p = pos[i];
+    if (p >= (uint32_t)K) return;                               // (a K that is not the record's: no write out of bounds)
+    tp[p] = (int)counts[(long long)i * RC_COLS + 0];
+    fp[p] = (int)counts[(long long)i * RC_COLS + 1];
+    thr[p] = score[i];
+}
+
+constexpr int CR_MAX_BLOCKS = 1024;     // workgroups of the two partial passes (a function of N only: the sums' order is fixed)
+constexpr int CR_INTS = 11;             // integer partials of a workgroup (CI_*)
+constexpr int CR_F64 = 4;               // fp64 partials of a workgroup
+constexpr int CR_WS_ROW = CR_INTS + CR_F64 + 3;   // + the workgroup's best-pF1 candidate (tp, fp, score bits)
+enum { CI_NPOS, CI_NNEG, CI_SUM_NEG_GE, CI_SUM_NEG_GT, CI_TP, CI_FP, CI_TN, CI_FN, CI_K, CI_NAN, CI_BADLABEL, CI_COUNT };
+static_assert(CI_COUNT == CR_INTS, "one partial per CI_* index");
+enum { REC_NPOS, REC_NNEG, REC_GT, REC_EQ, REC_BEST_TP, REC_BEST_FP, REC_BEST_THR, REC_TP, REC_FP, REC_TN, REC_FN, REC_K,
+       REC_NAN, REC_BADLABEL, REC_SPARE0, REC_SPARE1, REC_PRAUC, REC_AP, REC_CLIP_POS, REC_CLIP_NEG, REC_SLOTS };
+static_assert(REC_SLOTS == 20 && REC_PRAUC == 16, "record layout of include/mammoclip_hip.h");
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
+        v += ((u64)hi << 32) | lo;
+    }
+    return v;
+}
+// xor butterfly: every lane adds the same pairs in the same order on every call, so the sum's bits are fixed
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// sums of the 256 threads' values in thread 0 (waves combined in wave order through LDS)
+__device__ __forceinline__ u64 block_sum_u64(u64 v, u64* s4) {
+    v = wave_sum_u64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s4[0] + s4[1] + s4[2] + s4[3];
+}
+__device__ __forceinline__ double block_sum_f64(double v, double* s4) {
+    v = wave_sum_f64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((s4[0] + s4[1]) + s4[2]) + s4[3];
+}
+
+// best-pF1 candidate: 2 tp / (tp + fp + n_pos) compared as a cross product in 64-bit integers (tp, fp, n_pos <= 2^24: below
+// 2^50), the higher threshold on equal value.  (0, 0, -inf) is "none" and loses against every real candidate (tp >= 1).
+struct Best { uint32_t tp, fp; float thr; };
+__device__ __forceinline__ bool best_better(const Best& a, const Best& b, u64 npos) {
+    const u64 l = (u64)a.tp * ((u64)b.tp + b.fp + npos), r = (u64)b.tp * ((u64)a.tp + a.fp + npos);
+    return l > r || (l == r && a.thr > b.thr);
+}
+__device__ __forceinline__ Best best_shfl_xor(const Best& a, int o) {
+    Best b;
+    b.tp = __shfl_xor(a.tp, o, 64);
+    b.fp = __shfl_xor(a.fp, o, 64);
+    b.thr = __shfl_xor(a.thr, o, 64);
+    return b;
+}
+
+// pass 1: the workgroup's integer partials -> ws[block][0 .. CR_INTS).  counts may be null (the count columns read as 0).
+__global__ __launch_bounds__(256) void cls_partial_int_k(const float* __restrict__ score, const int* __restrict__ label,
+                                                         const uint32_t* __restrict__ counts, int N, double threshold,
+                                                         u64* __restrict__ ws) {
+    __shared__ u64 s4[4];
+    u64 v[CR_INTS];
+#pragma unroll
+    for (int q = 0; q < CR_INTS; ++q) v[q] = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
+        const float s = score[i];
+        const int lb = label[i];
+        const bool pos = lb != 0, pred = (double)s >= threshold;
+        v[CI_NPOS] += (u64)pos;
+        v[CI_NNEG] += (u64)!pos;
+        v[CI_TP] += (u64)(pos && pred);
+        v[CI_FN] += (u64)(pos && !pred);
+        v[CI_FP] += (u64)(!pos && pred);
+        v[CI_TN] += (u64)(!pos && !pred);
+        v[CI_NAN] += (u64)(s != s);
+        v[CI_BADLABEL] += (u64)(lb != 0 && lb != 1);
+        if (counts) {
+            const uint32_t* c = counts + i * RC_COLS;
+            if (pos) { v[CI_SUM_NEG_GE] += c[1]; v[CI_SUM_NEG_GT] += c[3]; }
+            v[CI_K] += (u64)(c[4] == 0);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < CR_INTS; ++q) {
+        const u64 t = block_sum_u64(v[q], s4);
+        if (threadIdx.x == 0) ws[(long long)blockIdx.x * CR_WS_ROW + q] = t;
+    }
+}
+
+// pass 2: n_pos from pass 1's partials, then the workgroup's fp64 partials (samples in a fixed order per thread, threads in a
+// fixed tree) and its best-pF1 candidate -> ws[block][CR_INTS ..)
+__global__ __launch_bounds__(256) void cls_partial_f64_k(const float* __restrict__ score, const int* __restrict__ label,
+                                                         const uint32_t* __restrict__ counts, int N, u64* __restrict__ ws) {
+    __shared__ u64 s4[4];
+    __shared__ double d4[4];
+    __shared__ Best b4[4];
+    u64 np = 0;
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += 256) np += ws[(long long)b * CR_WS_ROW + CI_NPOS];
+    const u64 npos = block_sum_u64(np, s4);
+    const double dn = (double)npos;
+    double f[CR_F64] = {0.0, 0.0, 0.0, 0.0};                    // PR-AUC, AP, sum of clipped scores over positives, negatives
+    Best best = {0u, 0u, -__builtin_inff()};
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
+        const float s = score[i];
+        const bool pos = label[i] != 0;
+        const double cs = (double)fminf(fmaxf(s, 0.f), 1.f);
+        f[2] += pos ? cs : 0.0;                                 // (+ 0.0 leaves a sum's bits as they are)
+        f[3] += pos ? 0.0 : cs;
+        if (!counts) continue;
+        const uint32_t* c = counts + i * RC_COLS;
+        const uint32_t tp1 = c[0], fp1 = c[1], tp0 = c[2], fp0 = c[3];
+        if (pos) {
+            const Best cand = {tp1, fp1, s};
+            if (best_better(cand, best, npos)) best = cand;
+        }
+        if (c[4] == 0 && npos && tp1 + fp1) {                   // the representative of its threshold (tp1 + fp1 == 0: NaN)
+            const double p1 = (double)tp1 / (double)(tp1 + fp1);
+            const double p0 = tp0 + fp0 ? (double)tp0 / (double)(tp0 + fp0) : 1.0;      // the curve's start: precision 1
+            const double dr = (double)tp1 / dn - (double)tp0 / dn;
+            f[0] += dr * (p1 + p0) / 2.0;
+            f[1] += dr * p1;
+        }
+    }
+    u64* row = ws + (long long)blockIdx.x * CR_WS_ROW + CR_INTS;
+#pragma unroll
+    for (int q = 0; q < CR_F64; ++q) {
+        const double t = block_sum_f64(f[q], d4);
+        if (threadIdx.x == 0) row[q] = (u64)__double_as_longlong(t);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const Best other = best_shfl_xor(best, o);
+        if (best_better(other, best, npos)) best = other;
+    }
+    if ((threadIdx.x & 63) == 0) b4[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (best_better(b4[w], best, npos)) best = b4[w];
+        row[CR_F64 + 0] = best.tp;
+        row[CR_F64 + 1] = best.fp;
+        row[CR_F64 + 2] = __float_as_uint(best.thr);
+    }
+}
+
+// pass 3, one workgroup: the partial rows in row order -> the record
+__global__ __launch_bounds__(256) void cls_final_k(const u64* __restrict__ ws, int blocks, int have_counts,
+                                                   u64* __restrict__ rec) {
+    __shared__ u64 s4[4];
+    __shared__ double d4[4];
+    __shared__ Best b4[4];
+    u64 tot[CR_INTS];
+#pragma unroll
+    for (int q = 0; q < CR_INTS; ++q) {
+        u64 v = 0;
+        for (int b = threadIdx.x; b < blocks; b += 256) v += ws[(long long)b * CR_WS_ROW + q];
+        tot[q] = block_sum_u64(v, s4);
+    }
+    double ftot[CR_F64];
+#pragma unroll
+    for (int q = 0; q < CR_F64; ++q) {
+        double v = 0.0;
+        for (int b = threadIdx.x; b < blocks; b += 256)
+            v += __longlong_as_double((long long)ws[(long long)b * CR_WS_ROW + CR_INTS + q]);
+        ftot[q] = block_sum_f64(v, d4);
+    }
+    const u64 npos = tot[CI_NPOS], nneg = tot[CI_NNEG];
+    Best best = {0u, 0u, -__builtin_inff()};
+    for (int b = threadIdx.x; b < blocks; b += 256) {
+        const u64* row = ws + (long long)b * CR_WS_ROW + CR_INTS + CR_F64;
+        const Best cand = {(uint32_t)row[0], (uint32_t)row[1], __uint_as_float((uint32_t)row[2])};
+        if (best_better(cand, best, npos)) best = cand;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const Best other = best_shfl_xor(best, o);
+        if (best_better(other, best, npos)) best = other;
+    }
+    if ((threadIdx.x & 63) == 0) b4[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < 4; ++w)
+        if (best_better(b4[w], best, npos)) best = b4[w];
+    const bool curve = have_counts && npos;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    rec[REC_NPOS] = npos;
+    rec[REC_NNEG] = nneg;
+    rec[REC_GT] = have_counts ? npos * nneg - tot[CI_SUM_NEG_GE] : 0;          // sum over positives of (n_neg - neg_ge)
+    rec[REC_EQ] = have_counts ? tot[CI_SUM_NEG_GE] - tot[CI_SUM_NEG_GT] : 0;    // sum over positives of (neg_ge - neg_gt)
+    rec[REC_BEST_TP] = best.tp;
+    rec[REC_BEST_FP] = best.fp;
+    rec[REC_BEST_THR] = __float_as_uint(best.thr);
+    rec[REC_TP] = tot[CI_TP];
+    rec[REC_FP] = tot[CI_FP];
+    rec[REC_TN] = tot[CI_TN];
+    rec[REC_FN] = tot[CI_FN];
+    rec[REC_K] = tot[CI_K];
+    rec[REC_NAN] = tot[CI_NAN];
+    rec[REC_BADLABEL] = tot[CI_BADLABEL];
+    rec[REC_SPARE0] = 0;
+    rec[REC_SPARE1] = 0;
+    rec[REC_PRAUC] = (u64)__double_as_longlong(curve ? ftot[0] : nan);
+    rec[REC_AP] = (u64)__double_as_longlong(curve ? ftot[1] : nan);
+    rec[REC_CLIP_POS] = (u64)__double_as_longlong(ftot[2]);
+    rec[REC_CLIP_NEG] = (u64)__double_as_longlong(ftot[3]);
+}
+
+constexpr int CLS_MAX_N = 1 << 24;      // counts fit 32 bits, count products fit fp64 (and 64-bit integers) exactly
+
 int g_splits = 0;   // 0: chosen per call
 
 }  // namespace
@@ -352,6 +632,55 @@ extern "C" int mc_auroc_counts(const float* score, const int* label, long long* 
     }
     hipLaunchKernelGGL(auroc_counts_k, dim3(mc_div_up(N, 256), mc_div_up(N, AUC_J)), dim3(256), 0, (hipStream_t)stream, score,
                        label, (u64*)counts, N);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_rank_counts(const float* score, const int* label, unsigned int* counts, int N, void* stream) {
+    MC_CHECK(score && label && counts, "rank_counts: null pointer");
+    MC_CHECK(N >= 1 && N <= CLS_MAX_N, "rank_counts: N outside [1, 2^24]");
+    if (hipMemsetAsync(counts, 0, (size_t)N * RC_COLS * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) {
+        mc_set_error("rank_counts: hipMemsetAsync failed");
+        return MC_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(rank_counts_k, dim3(mc_div_up(N, RC_I), mc_div_up(N, RC_J)), dim3(RC_I), 0, (hipStream_t)stream, score,
+                       label, counts, N);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" long long mc_cls_record_ws_bytes(int N) {
+    if (N < 1 || N > CLS_MAX_N) return 0;
+    return (long long)min(mc_div_up(N, 256), CR_MAX_BLOCKS) * CR_WS_ROW * (long long)sizeof(u64);
+}
+extern "C" int mc_cls_record(const float* score, const int* label, const unsigned int* counts, int N, double threshold,
+                             long long* record, void* ws, void* stream) {
+    MC_CHECK(score && label && record && ws, "cls_record: null pointer");
+    MC_CHECK(N >= 1 && N <= CLS_MAX_N, "cls_record: N outside [1, 2^24]");
+    MC_CHECK(threshold == threshold, "cls_record: the threshold is NaN");
+    const int blocks = min(mc_div_up(N, 256), CR_MAX_BLOCKS);
+    hipLaunchKernelGGL(cls_partial_int_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, score, label, counts, N, threshold,
+                       (u64*)ws);
+    MC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cls_partial_f64_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, score, label, counts, N, (u64*)ws);
+    MC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cls_final_k, dim3(1), dim3(256), 0, (hipStream_t)stream, (const u64*)ws, blocks, (int)(counts != nullptr),
+                       (u64*)record);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_cls_curve(const float* score, const unsigned int* counts, int N, int K, unsigned int* pos_ws, int* tp, int* fp,
+                            float* threshold, void* stream) {
+    MC_CHECK(score && counts && pos_ws && tp && fp && threshold, "cls_curve: null pointer");
+    MC_CHECK(N >= 1 && N <= CLS_MAX_N, "cls_curve: N outside [1, 2^24]");
+    MC_CHECK(K >= 1 && K <= N, "cls_curve: K outside [1, N]");
+    if (hipMemsetAsync(pos_ws, 0, (size_t)N * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) {
+        mc_set_error("cls_curve: hipMemsetAsync failed");
+        return MC_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(rep_rank_k, dim3(mc_div_up(N, RC_I), mc_div_up(N, RC_J)), dim3(RC_I), 0, (hipStream_t)stream, score, counts,
+                       pos_ws, N);
+    MC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(curve_scatter_k, dim3(mc_div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, score, counts,
+                       (const uint32_t*)pos_ws, N, K, tp, fp, threshold);
     MC_LAUNCH_CHECK();
     return MC_OK;
 }

@@ -248,6 +248,10 @@ _SIGS = {
     "mc_sim_set_splits": ([I], I),
     "mc_sim_softmax": ([P, P, P, I, I, I, P], I),
     "mc_auroc_counts": ([P, P, P, I, P], I),
+    "mc_rank_counts": ([P, P, P, I, P], I),
+    "mc_cls_record_ws_bytes": ([I], LL),
+    "mc_cls_record": ([P, P, P, I, D, P, P, P], I),
+    "mc_cls_curve": ([P, P, I, I, P, P, P, P, P], I),
     "mc_augment_ws_bytes": ([I, I, I], LL),
     "mc_augment_u8": ([P, LL, LL, LL, I, P, I, P, I, I, I, P, P, LL, P], I),
     "mc_augment_set_stages": ([I], I),

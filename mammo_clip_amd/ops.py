@@ -1693,6 +1693,65 @@ def auroc_counts(score, label):
     return counts
 
 
+CLS_RECORD_INTS = ("n_pos", "n_neg", "gt", "eq", "best_tp", "best_fp", "best_threshold", "tp", "fp", "tn", "fn", "k", "n_nan",
+                   "n_bad_label")                                   # slots 0..13 of the record; 14, 15 are spare
+CLS_RECORD_F64 = ("prauc", "ap", "clip_pos", "clip_neg")             # slots 16..19, fp64 bits
+
+
+def _score_label(what, score, label):
+    _chk_dev(score, label)
+    if score.dtype != torch.float32 or score.dim() != 1 or not score.is_contiguous():
+        raise L.MammoClipHipError(f"{what}: contiguous fp32 [N] scores")
+    label = label.to(device=score.device, dtype=torch.int32).contiguous()
+    if label.shape != score.shape:
+        raise L.MammoClipHipError(f"{what}: one label per score")
+    return label
+
+
+def _rank_counts_arg(what, score, counts):
+    if counts.dtype != torch.int32 or counts.shape != (score.numel(), 5) or not counts.is_contiguous() \
+            or counts.device != score.device:
+        raise L.MammoClipHipError(f"{what}: counts is what rank_counts returned for these scores (int32 [N, 5])")
+
+
+def rank_counts(score, label):
+    """int32 [N, 5] on the device, per sample i: positives with s_j >= s_i, negatives with s_j >= s_i (i included), the same
+    two with s_j > s_i, and the number of j < i with s_j == s_i (0: i represents its distinct score).  1 <= N <= 2^24."""
+    label = _score_label("rank_counts", score, label)
+    counts = empty((score.numel(), 5), torch.int32, score)
+    L.call("mc_rank_counts", _p(score), _p(label), _p(counts), score.numel(), _st())
+    return counts
+
+
+def cls_record(score, label, counts=None, threshold=0.5):
+    """int64 [20] on the device: the integers CLS_RECORD_INTS, two spare slots, then the fp64 values CLS_RECORD_F64 (their
+    bits: ``record[16:].view(torch.float64)``).  ``counts``: what rank_counts returned, or None for the fields that need no
+    counts alone.  Bit-reproducible (include/mammoclip_hip.h: mc_cls_record)."""
+    label = _score_label("cls_record", score, label)
+    if counts is not None:
+        _rank_counts_arg("cls_record", score, counts)
+    n = score.numel()
+    record = empty((20,), torch.int64, score)
+    ws = empty((max(1, L.load().mc_cls_record_ws_bytes(n)),), torch.uint8, score)
+    L.call("mc_cls_record", _p(score), _p(label), _p(counts), n, float(threshold), _p(record), _p(ws), _st())
+    return record
+
+
+def cls_curve(score, counts, k):
+    """(tp int32 [k], fp int32 [k], threshold fp32 [k]) on the device: the counts of every distinct score, ascending; ``k`` is
+    the record's number of distinct scores"""
+    _chk_dev(score, counts)
+    if score.dtype != torch.float32 or score.dim() != 1 or not score.is_contiguous():
+        raise L.MammoClipHipError("cls_curve: contiguous fp32 [N] scores")
+    _rank_counts_arg("cls_curve", score, counts)
+    n, k = score.numel(), int(k)
+    kk = max(k, 1)                                                   # (a bad k fails in the call)
+    tp, fp, thr = empty((kk,), torch.int32, score), empty((kk,), torch.int32, score), empty((kk,), torch.float32, score)
+    pos = empty((max(n, 1),), torch.int32, score)
+    L.call("mc_cls_curve", _p(score), _p(counts), n, k, _p(pos), _p(tp), _p(fp), _p(thr), _st())
+    return tp, fp, thr
+
+
 # ------------------------------------------------------------------------------------------- training augmentation
 def augment_u8(src, params, sigma, out=None, ws_bytes=None):
     """uint8 [n, 3, H, W]: flips / affine / elastic warp of the planes ``src`` (uint8 [n_src, H, W], any strides) under the
