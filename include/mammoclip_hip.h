@@ -865,6 +865,31 @@ int mc_grads_scale_dev(const mc_adamw_tensor* tensors, int n_tensors, const floa
 int mc_adamw_step_clip(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps,
                        double weight_decay, long long step, const float* grad_coef, const float* found_inf,
                        const float* skipped, void* stream);
+/* Exponential moving average of the weights (a shadow model), kept by the optimizer step with no host read.
+ * CONTRACT.  For a tensor value p after the optimizer step and its fp32 shadow e, one applied update is three separately
+ * rounded fp32 operations, never fused:  s = p - e;  t = w * s;  e = e + t  -- what three tensor operations of torch give on
+ * any IEEE host.  w = (float)(1.0 - d_k) with d_k = min(decay, (1.0 + k) / (10.0 + k)) when warmup != 0 and d_k = decay
+ * otherwise, in double; k = *count + 1, where *count (a device int64 the caller owns) is the number of updates applied so
+ * far.  0 < decay < 1.  Every launch of one update reads *count; mc_ema_tick advances it once, last.  When found_inf is given
+ * and *found_inf != 0 (the step the loss scaler skips) no shadow changes and the count stays -- so the tick has to run before
+ * mc_loss_scale_update clears the flag.  The count is independent of the optimizer's own `skipped` counter.
+ *   mc_adamw_step_ema : the AdamW pass with the shadow update of the same element folded in: `shadows` is a HOST array of
+ *                       device pointers parallel to `tensors` (shadows[i] belongs to tensors[i].param; vector path when it is
+ *                       16-byte aligned like the others).  grad_coef is optional (NULL: no clip); found_inf / skipped are both
+ *                       NULL or both set, as in mc_adamw_step_clip.  Parameters, moments and bf16 images come out bit-equal to
+ *                       mc_adamw_step / _ls / _clip with the same arguments.
+ *   mc_ema_update     : the stand-alone form over HOST arrays of shadow pointers, source pointers and element counts (buffers,
+ *                       parameters the optimizer pass did not cover, other optimizers); found_inf is optional.  Same packing,
+ *                       vector path when both pointers of a tensor are 16-byte aligned.
+ *   mc_ema_tick       : *count += 1 unless *found_inf != 0 (found_inf optional); one thread.
+ * Every argument is checked before the first launch: NULL lists with n_tensors > 0, a decay outside (0, 1) or nan, a NULL
+ * count, negative sizes, NULL pointers of non-empty tensors. */
+int mc_adamw_step_ema(const mc_adamw_tensor* tensors, float* const* shadows, int n_tensors, double lr, double beta1, double beta2,
+                      double eps, double weight_decay, long long step, double decay, int warmup, const long long* count,
+                      const float* grad_coef, const float* found_inf, const float* skipped, void* stream);
+int mc_ema_update(float* const* shadows, const float* const* sources, const long long* numel, int n_tensors, double decay,
+                  int warmup, const long long* count, const float* found_inf, void* stream);
+int mc_ema_tick(long long* count, const float* found_inf, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
   ops.py         tensor-level wrappers (device memory + streams from torch, compute from HIP kernels)
   breastclip/    host-side mirror of the reference's ``breastclip`` model / loss API
   engine.py      data-parallel training step (RCCL) used by bench.py
+  ema.py         weight EMA: the shadow model the optimizer step keeps (off by default)
 """
 from . import lib  # noqa: F401
 

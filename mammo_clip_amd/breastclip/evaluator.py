@@ -24,15 +24,19 @@ log = logging.getLogger(__name__)
 
 
 class Evaluator:
-    def __init__(self, model=None, ckpt_path: Optional[str] = None, tokenizer=None, device=None):
+    def __init__(self, model=None, ckpt_path: Optional[str] = None, tokenizer=None, device=None, use_ema: bool = False):
         """Either an already built model, or a reference-layout checkpoint (``{"model", "config", ...}``,
-        trainer.py:215-237) whose ``config["model"]`` / ``config["loss"]`` rebuild it [ref: evaluator.py:24-27,52-58]."""
+        trainer.py:215-237) whose ``config["model"]`` / ``config["loss"]`` rebuild it [ref: evaluator.py:24-27,52-58].
+        ``use_ema``: load the averaged weights ``"model_ema"`` of the checkpoint (``checkpoint.save_checkpoint(ema=)``) instead
+        of ``"model"``; KeyError when the file has none.  (An averaged model in memory is just a model: ``model=ema.module``.)"""
         self.device = torch.device("cuda") if device is None else torch.device(device)
         if model is None:
             ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
+            if use_ema and "model_ema" not in ckpt:
+                raise KeyError(f"{ckpt_path} was saved without averaged weights (no 'model_ema')")
             self.ckpt_config = ckpt["config"]
             model = build_model(self.ckpt_config["model"], self.ckpt_config["loss"], tokenizer)
-            sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in ckpt["model"].items()}
+            sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in ckpt["model_ema" if use_ema else "model"].items()}
             model.load_state_dict(sd, strict=False)                       # evaluator.py:151 uses strict=False
         self.model = model.to(self.device).eval()
 

@@ -6,6 +6,8 @@ that behaviour is kept.
 and ``state_dict()`` layout as ``torch.optim.AdamW`` (state per parameter: ``step``, ``exp_avg``, ``exp_avg_sq``), so
 optimizer checkpoints move both ways [ref: trainer.py:215-237 stores ``optimizer.state_dict()``], with the update done
 by one multi-tensor HIP kernel per 40 parameters (``mc_adamw_step``)."""
+import ctypes
+import weakref
 from typing import Dict
 
 import torch
@@ -83,13 +85,29 @@ class AdamW(torch.optim.Optimizer):
         self._plans[gi] = plan
         return plan
 
+    def _ema_table(self, plan, ema):
+        """the shadow pointers of ``plan``'s parameters, parallel to its tensor table; cached with the plan and validated like
+        its other raw pointers (a shadow moved or replaced changes data_ptr)"""
+        tab = plan.get("ema")
+        if tab is not None and tab["of"]() is ema and len(tab["shadows"]) == len(plan["params"]) and \
+                all(e.data_ptr() == ptr for e, ptr in zip(tab["shadows"], tab["ptrs"])):
+            return tab
+        shadows = ema.shadows_for(plan["params"])
+        for p, e in zip(plan["params"], shadows):
+            if e.numel() != p.numel() or e.data_ptr() == p.data_ptr():
+                raise L.MammoClipHipError("AdamW: an EMA shadow must be a tensor of its own with the parameter's size")
+        ptrs = [e.data_ptr() for e in shadows]
+        tab = plan["ema"] = {"of": weakref.ref(ema), "shadows": shadows, "ptrs": ptrs,
+                             "arr": (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)}
+        return tab
+
     @torch.no_grad()
-    def step_loss_scaled(self, scaler, grad_coef=None):
+    def step_loss_scaled(self, scaler, grad_coef=None, ema=None):
         """``step()`` under an ``engine.LossScaler`` without a host sync: the kernel reads the scaler's non-finite flag and
         does nothing on a bad step (GradScaler.step() would not call optimizer.step()); its bias corrections use the
         number of APPLIED steps = attempted steps (counted on the host) - skipped steps (counted on the device, in a tensor
         this optimizer owns: it survives a change of scaler).  Returns that counter for ``scaler.update``.
-        ``grad_coef``: as in ``step``."""
+        ``grad_coef``, ``ema``: as in ``step``; on a skipped step the shadows stay as they are, like the parameters."""
         dev = self.param_groups[0]["params"][0].device
         if getattr(self, "_ls_skipped", None) is None or self._ls_skipped.device != dev:
             self._fold_skipped()                           # (a counter on another device: fold it into the host counts)
@@ -97,7 +115,7 @@ class AdamW(torch.optim.Optimizer):
         st = scaler.state(dev)
         self._ls = (st.data_ptr() + 4 * scaler._FLAG, self._ls_skipped.data_ptr())
         try:
-            self.step(grad_coef=grad_coef)
+            self.step(grad_coef=grad_coef, ema=ema)
         finally:
             self._ls = None
         return self._ls_skipped
@@ -108,9 +126,12 @@ class AdamW(torch.optim.Optimizer):
         self._ls_skipped = None
 
     @torch.no_grad()
-    def step(self, closure=None, grad_coef=None):
+    def step(self, closure=None, grad_coef=None, ema=None):
         """``grad_coef``: a 1-element fp32 device tensor (the clip coefficient of ``ops.grad_norm_coef``); every gradient is
-        multiplied by it as the kernel loads it (``mc_adamw_step_clip``), ``p.grad`` itself is left as it is."""
+        multiplied by it as the kernel loads it (``mc_adamw_step_clip``), ``p.grad`` itself is left as it is.
+        ``ema``: a ``mammo_clip_amd.ema.ModelEma`` of the model these parameters belong to: the launch is ``mc_adamw_step_ema``,
+        which also moves the shadow of every element it updates; ``ema.update(model)`` afterwards does the tensors this pass
+        did not cover and advances the count of updates."""
         loss = None
         if grad_coef is not None and not (torch.is_tensor(grad_coef) and grad_coef.is_cuda and grad_coef.dtype == torch.float32
                                           and grad_coef.numel() >= 1):
@@ -146,17 +167,26 @@ class AdamW(torch.optim.Optimizer):
             stream = torch.cuda.current_stream().cuda_stream
             hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
             ls = getattr(self, "_ls", None)
-            if grad_coef is not None:
+            tab = self._ema_table(plan, ema) if ema is not None else None
+            if tab is not None:
+                # (the table of shadow pointers goes in front of the count; every optional pointer may be None)
+                entry = "mc_adamw_step_ema"
+                tail = (float(ema.decay), int(ema.warmup), ema.count_ptr(), grad_coef.data_ptr() if grad_coef is not None else None,
+                        ls[0] if ls else None, ls[1] if ls else None, stream)
+            elif grad_coef is not None:
                 entry, tail = "mc_adamw_step_clip", (grad_coef.data_ptr(), ls[0] if ls else None, ls[1] if ls else None, stream)
             else:
                 entry, tail = ("mc_adamw_step_ls", (ls[0], ls[1], stream)) if ls else ("mc_adamw_step", (stream,))
             if min(steps) == max(steps):
-                L.call(entry, arr, len(params), *hyper, steps[0], *tail)
+                L.call(entry, arr, *((tab["arr"],) if tab else ()), len(params), *hyper, steps[0], *tail)
             else:                                             # parameters that joined later: one launch set per step count
                 for t in sorted(set(steps)):
                     idx = [i for i, s_ in enumerate(steps) if s_ == t]
                     sub = (L.AdamwTensor * len(idx))(*[arr[i] for i in idx])
-                    L.call(entry, sub, len(idx), *hyper, t, *tail)
+                    ssub = ((ctypes.c_void_p * len(idx))(*[tab["ptrs"][i] for i in idx]),) if tab else ()
+                    L.call(entry, sub, *ssub, len(idx), *hyper, t, *tail)
+            if tab is not None:
+                ema.mark_covered(params, tab["shadows"])       # (bumps the shadows' version counters, as below)
             # the kernel wrote through raw pointers: tell autograd (and the derived-weight-image cache in ops.py,
             # which keys on the version counter) that these tensors changed in place
             torch.autograd.graph.increment_version(params)

@@ -13,10 +13,13 @@ import torch
 
 
 def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, scheduler=None, config: Optional[Dict] = None,
-                    epoch: int = 0, train_loss: float = 0.0, best: bool = False, scaler=None) -> str:
+                    epoch: int = 0, train_loss: float = 0.0, best: bool = False, scaler=None, ema=None) -> str:
     """``scaler``: an ``engine.LossScaler`` (f16 storage build) -- its state goes under the extra key ``"scaler"`` like the
     reference's GradScaler would have to be saved for an exact resume (the reference itself resumes model weights only,
-    SURVEY.md appendix B 9; readers of the reference layout ignore the key)."""
+    SURVEY.md appendix B 9; readers of the reference layout ignore the key).
+    ``ema``: an ``ema.ModelEma`` -- the averaged weights go under ``"model_ema"``, a state dict in the layout of ``"model"`` that
+    loads anywhere ``"model"`` does, and decay, warm-up and the count of applied updates under ``"ema"``; ``"model"`` itself is
+    what it is without them, and readers of the reference layout ignore both keys."""
     sd = {k: v.detach().to("cpu") for k, v in model.state_dict().items()}
     ckpt = {"model": sd,
             "optimizer": optimizer.state_dict() if optimizer is not None else None,
@@ -24,6 +27,10 @@ def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, scheduler
             "config": config, "epoch": int(epoch), "train_loss": float(train_loss)}
     if scaler is not None:
         ckpt["scaler"] = scaler.state_dict()
+    if ema is not None:
+        esd = ema.state_dict()
+        ckpt["model_ema"] = esd.pop("module")
+        ckpt["ema"] = esd
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(ckpt, path)
     if best:                                   # "<name>-best.tar" beside it, like the reference
@@ -32,7 +39,7 @@ def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, scheduler
     return path
 
 
-def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, scheduler=None, strict: bool = True, scaler=None) -> Dict:
+def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, scheduler=None, strict: bool = True, scaler=None, ema=None) -> Dict:
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     sd = ckpt["model"] if "model" in ckpt else ckpt
     sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}     # DDP-wrapped saves
@@ -43,4 +50,8 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, scheduler
         scheduler.load_state_dict(ckpt["scheduler"])
     if scaler is not None and ckpt.get("scaler") is not None:
         scaler.load_state_dict(ckpt["scaler"])
+    if ema is not None:
+        if "model_ema" not in ckpt or "ema" not in ckpt:
+            raise KeyError(f"{path} was saved without averaged weights (no 'model_ema' / 'ema')")
+        ema.load_state_dict(dict(ckpt["ema"], module=ckpt["model_ema"]))
     return ckpt

@@ -4,7 +4,11 @@
 // B5 + BERT model; a parameter that is consumed as a bf16 matrix gets its bf16 image rewritten by the same pass (+2 B)
 // instead of by a cast kernel of its own in the next forward.  Up to PACK tensors go into one launch (pointers travel as kernel arguments, no device
 // table to keep in sync); a workgroup owns one CHUNK of one tensor, found by a scan over the pack's chunk prefix.
+// mc_adamw_step_ema folds an exponential moving average of the weights into the same pass: the shadow of every updated
+// element is read and written while the parameter is still in registers (+8 B per element, no second read of the parameter);
+// mc_ema_update is the stand-alone form for tensors the optimizer pass does not cover (12 B per element).
 #include <cfloat>
+#include <type_traits>
 #include "common_hip.h"
 #include "../../include/mammoclip_hip.h"
 
@@ -32,11 +36,17 @@ struct AdamScalars {
     float eps;
 };
 
+// FORM: how the sum of two products in the second moment is contracted.  0 leaves it to the compiler, which under
+// -ffp-contract=fast takes fma(beta2, v, (c g) g) in some bodies of the kernel and fma(c g, g, beta2 v) in others (1 and 2:
+// each written out) -- two roundings that differ in the last bit.  Every other expression has one product per sum.
+template <int FORM = 0>
 __device__ __forceinline__ void adamw1(float& p, float g, float& m, float& v, const AdamScalars& s) {
     // same operation order as torch's AdamW: decoupled decay first, moments, then the bias-corrected step
     p -= s.lr_wd * p;
     m = m + s.one_m_beta1 * (g - m);
-    v = s.beta2 * v + s.one_m_beta2 * g * g;
+    if (FORM == 1) v = __builtin_fmaf(s.beta2, v, (s.one_m_beta2 * g) * g);
+    else if (FORM == 2) v = __builtin_fmaf(s.one_m_beta2 * g, g, s.beta2 * v);
+    else v = s.beta2 * v + s.one_m_beta2 * g * g;
     const float denom = sqrtf(v) * s.inv_bc2_sqrt + s.eps;
     p -= s.step_size * (m / denom);
 }
@@ -62,10 +72,43 @@ __device__ __forceinline__ void mul_rn4(float4& g, float c) {
     g.x = mul_rn(g.x, c); g.y = mul_rn(g.y, c); g.z = mul_rn(g.z, c); g.w = mul_rn(g.w, c);
 }
 
+// Weight EMA: e <- e + w * (p - e) as three separately rounded fp32 operations (sub, mul, add: what three tensor operations of
+// torch give on any IEEE host).  The product is the instruction, like the clip product above: under -ffp-contract=fast a C++
+// product would be fused into the sum that consumes it.  w = (float)(1 - d_k), d_k = min(decay, (1 + k) / (10 + k)) with
+// warm-up, decay without, in double; k = *count + 1: the applied updates so far, a device integer, plus this one.  Every
+// launch of one update reads the same count; mc_ema_tick advances it afterwards.
+struct NoEma {};
+struct AdamEma {
+    float* e[PACK];                  // shadow of pk.p[t]
+    const long long* count;
+    double decay;
+    int warmup;
+};
+
+__device__ __forceinline__ float ema_weight(const long long* __restrict__ count, double decay, int warmup) {
+    double d = decay;
+    if (warmup) {
+        const double k = (double)(*count + 1);
+        const double r = (1.0 + k) / (10.0 + k);
+        if (r < d) d = r;
+    }
+    return (float)(1.0 - d);
+}
+__device__ __forceinline__ void ema1(float& e, float p, float w) {
+    float s = p - e;
+    asm("v_mul_f32 %0, %1, %0" : "+v"(s) : "v"(w));      // (w comes out of fp64 arithmetic: a vector register)
+    e = e + s;
+}
+__device__ __forceinline__ void ema4(float4& e, const float4& p, float w) {
+    ema1(e.x, p.x, w); ema1(e.y, p.y, w); ema1(e.z, p.z, w); ema1(e.w, p.w, w);
+}
+
 // CLIP: every gradient is multiplied by *ls.grad_coef as it is loaded (gradient-norm clipping without rewriting the
-// gradients in memory); CLIP = false is the kernel as it was.
-template <bool CLIP>
-__global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, AdamScalars s, AdamLs ls) {
+// gradients in memory); CLIP = false is the kernel as it was.  EMA: the shadow em.e[t] of every updated element follows in the
+// same pass (a skipped step returns before it, like before everything else); EMA = false is the kernel as it was.
+template <bool CLIP, bool EMA>
+__global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, AdamScalars s, AdamLs ls,
+                                                     std::conditional_t<EMA, AdamEma, NoEma> em) {
     if (ls.found_inf) {
         if (*ls.found_inf != 0.f) return;                              // (uniform: the whole grid leaves)
         __shared__ float s_dev[2];
@@ -80,6 +123,13 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
         s.inv_bc2_sqrt = s_dev[1];
     }
     const float c = CLIP ? *ls.grad_coef : 1.f;
+    // The instantiations without EMA are compiled as they always were (FORM 0).  Those with EMA have to give their results
+    // bit for bit, and the extra loads move the compiler's choice, so each body is pinned to what its counterpart compiles to:
+    // the vector bodies of the plain kernel to form 2, its ragged tail and scalar body and all of the clip kernel to form 1
+    // (read off the generated code of both; tests/test_ema_gpu.py compares the bits on every path).
+    constexpr int FV = !EMA ? 0 : CLIP ? 1 : 2, FS = !EMA ? 0 : 1;
+    float w = 0.f;
+    if constexpr (EMA) w = ema_weight(em.count, em.decay, em.warmup);
     int t = 0;
     const int blk = blockIdx.x;
     while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;       // uniform scan, <= PACK scalar compares
@@ -92,7 +142,9 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
     bf16_t* __restrict__ img = pk.img[t] ? pk.img[t] + base : nullptr;      // base is a multiple of 16384: alignment kept
     const long long left = n - base;
     const int len = left < CHUNK ? (int)left : CHUNK;
-    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0 &&
+    float* __restrict__ e = nullptr;
+    if constexpr (EMA) e = em.e[t] + base;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)e)) & 15) == 0 &&
                      (((uintptr_t)img) & 7) == 0;
     int i = threadIdx.x * 4;
     if (vec) {
@@ -102,14 +154,20 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
             float4 G0 = *(const float4*)(g + i), G1 = *(const float4*)(g + i + 1024);
             float4 M0 = *(const float4*)(m + i), M1 = *(const float4*)(m + i + 1024);
             float4 V0 = *(const float4*)(v + i), V1 = *(const float4*)(v + i + 1024);
+            float4 E0, E1;
+            if constexpr (EMA) { E0 = *(const float4*)(e + i); E1 = *(const float4*)(e + i + 1024); }
             if (CLIP) { mul_rn4(G0, c); mul_rn4(G1, c); }
-            adamw1(P0.x, G0.x, M0.x, V0.x, s); adamw1(P0.y, G0.y, M0.y, V0.y, s);
-            adamw1(P0.z, G0.z, M0.z, V0.z, s); adamw1(P0.w, G0.w, M0.w, V0.w, s);
-            adamw1(P1.x, G1.x, M1.x, V1.x, s); adamw1(P1.y, G1.y, M1.y, V1.y, s);
-            adamw1(P1.z, G1.z, M1.z, V1.z, s); adamw1(P1.w, G1.w, M1.w, V1.w, s);
+            adamw1<FV>(P0.x, G0.x, M0.x, V0.x, s); adamw1<FV>(P0.y, G0.y, M0.y, V0.y, s);
+            adamw1<FV>(P0.z, G0.z, M0.z, V0.z, s); adamw1<FV>(P0.w, G0.w, M0.w, V0.w, s);
+            adamw1<FV>(P1.x, G1.x, M1.x, V1.x, s); adamw1<FV>(P1.y, G1.y, M1.y, V1.y, s);
+            adamw1<FV>(P1.z, G1.z, M1.z, V1.z, s); adamw1<FV>(P1.w, G1.w, M1.w, V1.w, s);
             *(float4*)(p + i) = P0; *(float4*)(p + i + 1024) = P1;
             *(float4*)(m + i) = M0; *(float4*)(m + i + 1024) = M1;
             *(float4*)(v + i) = V0; *(float4*)(v + i + 1024) = V1;
+            if constexpr (EMA) {
+                ema4(E0, P0, w); ema4(E1, P1, w);
+                *(float4*)(e + i) = E0; *(float4*)(e + i + 1024) = E1;
+            }
             if (img) {
                 *(uint2*)(img + i) = make_uint2(pack_bf2(P0.x, P0.y), pack_bf2(P0.z, P0.w));
                 *(uint2*)(img + i + 1024) = make_uint2(pack_bf2(P1.x, P1.y), pack_bf2(P1.z, P1.w));
@@ -118,10 +176,13 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
         for (; i + 3 < len; i += 1024) {
             float4 P0 = *(const float4*)(p + i), G0 = *(const float4*)(g + i);
             float4 M0 = *(const float4*)(m + i), V0 = *(const float4*)(v + i);
+            float4 E0;
+            if constexpr (EMA) E0 = *(const float4*)(e + i);
             if (CLIP) mul_rn4(G0, c);
-            adamw1(P0.x, G0.x, M0.x, V0.x, s); adamw1(P0.y, G0.y, M0.y, V0.y, s);
-            adamw1(P0.z, G0.z, M0.z, V0.z, s); adamw1(P0.w, G0.w, M0.w, V0.w, s);
+            adamw1<FV>(P0.x, G0.x, M0.x, V0.x, s); adamw1<FV>(P0.y, G0.y, M0.y, V0.y, s);
+            adamw1<FV>(P0.z, G0.z, M0.z, V0.z, s); adamw1<FV>(P0.w, G0.w, M0.w, V0.w, s);
             *(float4*)(p + i) = P0; *(float4*)(m + i) = M0; *(float4*)(v + i) = V0;
+            if constexpr (EMA) { ema4(E0, P0, w); *(float4*)(e + i) = E0; }
             if (img) *(uint2*)(img + i) = make_uint2(pack_bf2(P0.x, P0.y), pack_bf2(P0.z, P0.w));
         }
         // ragged tail of the chunk: the (< 4) elements after the last whole float4
@@ -129,18 +190,72 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
         const int j = done + threadIdx.x;
         if (j < len) {
             float P = p[j], M = m[j], V = v[j];
-            adamw1(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
+            adamw1<FS>(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
             p[j] = P; m[j] = M; v[j] = V;
+            if constexpr (EMA) { float E = e[j]; ema1(E, P, w); e[j] = E; }
             if (img) img[j] = f2bf(P);
         }
     } else {
         for (int j = threadIdx.x; j < len; j += 256) {
             float P = p[j], M = m[j], V = v[j];
-            adamw1(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
+            adamw1<FS>(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
             p[j] = P; m[j] = M; v[j] = V;
+            if constexpr (EMA) { float E = e[j]; ema1(E, P, w); e[j] = E; }
             if (img) img[j] = f2bf(P);
         }
     }
+}
+
+// ---- stand-alone weight EMA: shadow <- shadow + w * (source - shadow) for a list of tensors (buffers, parameters the optimizer
+// pass did not cover, loops under another optimizer).  Same packing; 8 B read + 4 B written per element.  A set non-finite
+// flag makes the launch a no-op, like the optimizer step it follows.
+struct EmaPack {
+    float* e[PACK];
+    const float* p[PACK];
+    int first_chunk[PACK + 1];
+    long long n[PACK];
+};
+
+__global__ void __launch_bounds__(256) ema_multi_k(EmaPack pk, int count, const long long* __restrict__ applied, double decay,
+                                                   int warmup, const float* __restrict__ found_inf) {
+    if (found_inf && *found_inf != 0.f) return;                        // (uniform: the whole grid leaves)
+    const float w = ema_weight(applied, decay, warmup);
+    int t = 0;
+    const int blk = blockIdx.x;
+    while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;
+    const long long base = (long long)(blk - pk.first_chunk[t]) * CHUNK;
+    float* __restrict__ e = pk.e[t] + base;
+    const float* __restrict__ p = pk.p[t] + base;
+    const long long left = pk.n[t] - base;
+    const int len = left < CHUNK ? (int)left : CHUNK;
+    int i = threadIdx.x * 4;
+    if (((((uintptr_t)e) | ((uintptr_t)p)) & 15) == 0) {
+        // 4 float4 per array in flight per lane (8 loads) before the first use, like the optimizer pass
+        for (; i + 3 * 1024 + 3 < len; i += 4096) {
+            float4 E[4], P[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { E[u] = *(const float4*)(e + i + u * 1024); P[u] = *(const float4*)(p + i + u * 1024); }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { ema4(E[u], P[u], w); *(float4*)(e + i + u * 1024) = E[u]; }
+        }
+        for (; i + 3 < len; i += 1024) {
+            float4 E0 = *(const float4*)(e + i);
+            const float4 P0 = *(const float4*)(p + i);
+            ema4(E0, P0, w);
+            *(float4*)(e + i) = E0;
+        }
+        const int j = (len & ~3) + threadIdx.x;
+        if (j < len) { float E0 = e[j]; ema1(E0, p[j], w); e[j] = E0; }
+    } else {
+        for (int j = threadIdx.x; j < len; j += 256) { float E0 = e[j]; ema1(E0, p[j], w); e[j] = E0; }
+    }
+}
+
+// the count of applied updates moves on unless the step was skipped (one thread; before mc_loss_scale_update clears the flag)
+__global__ void ema_tick_k(long long* __restrict__ applied, const float* __restrict__ found_inf) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (found_inf && *found_inf != 0.f) return;
+    *applied += 1;
 }
 
 // ---- gradient unscale + non-finite check of the loss-scaled (f16 storage) step [ref: trainer.py:271-278 runs the backward
@@ -284,8 +399,15 @@ enum GradPass { GP_UNSCALE, GP_UNSCALE_NORM, GP_NORM };
 int grads_pass_impl(GradPass mode, const mc_adamw_tensor* tensors, int n_tensors, float mul, const float* scale_dev,
                     const float* mul_dev, float* found_inf, double* partials, void* stream);
 int grad_norm_finish(const double* partials, long long n, float max_norm, float* out2, void* stream);
+struct EmaHost {                       // the EMA arguments of a call (nullptr: none)
+    float* const* shadows;             // parallel to the tensor list
+    double decay;
+    int warmup;
+    const long long* count;
+};
 int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
-               long long step, const float* grad_coef, const float* found_inf, const float* skipped, void* stream);
+               long long step, const float* grad_coef, const float* found_inf, const float* skipped, const EmaHost* ema, void* stream);
+inline bool ema_decay_ok(double decay) { return decay > 0.0 && decay < 1.0; }            // (false for nan)
 
 // chunks (= doubles of norm workspace) of a gradient list, -1 on a bad one; need_grad: every non-empty tensor has a pointer
 long long list_chunks(const mc_adamw_tensor* tensors, int n_tensors, bool need_grad) {
@@ -399,14 +521,14 @@ int grad_norm_finish(const double* partials, long long n, float max_norm, float*
 
 extern "C" int mc_adamw_step(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
                              double eps, double weight_decay, long long step, void* stream) {
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, nullptr, stream);
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mc_adamw_step_ls(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
                                 double eps, double weight_decay, long long step, const float* found_inf, const float* skipped,
                                 void* stream) {
     MC_CHECK(found_inf && skipped, "adamw_step_ls: null loss-scale state");
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, found_inf, skipped, stream);
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, found_inf, skipped, nullptr, stream);
 }
 
 extern "C" int mc_adamw_step_clip(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
@@ -414,12 +536,69 @@ extern "C" int mc_adamw_step_clip(const mc_adamw_tensor* tensors, int n_tensors,
                                   const float* skipped, void* stream) {
     MC_CHECK(grad_coef, "adamw_step_clip: null grad_coef");
     MC_CHECK((found_inf == nullptr) == (skipped == nullptr), "adamw_step_clip: found_inf and skipped are both null or both set");
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, stream);
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, nullptr, stream);
+}
+
+extern "C" int mc_adamw_step_ema(const mc_adamw_tensor* tensors, float* const* shadows, int n_tensors, double lr, double beta1,
+                                 double beta2, double eps, double weight_decay, long long step, double decay, int warmup,
+                                 const long long* count, const float* grad_coef, const float* found_inf, const float* skipped,
+                                 void* stream) {
+    MC_CHECK(n_tensors >= 0 && ((tensors && shadows) || n_tensors == 0), "adamw_step_ema: bad tensor or shadow list");
+    MC_CHECK(ema_decay_ok(decay), "adamw_step_ema: decay must lie strictly between 0 and 1");
+    MC_CHECK(count, "adamw_step_ema: null update count");
+    MC_CHECK((found_inf == nullptr) == (skipped == nullptr), "adamw_step_ema: found_inf and skipped are both null or both set");
+    for (int i = 0; i < n_tensors; ++i) {
+        MC_CHECK(tensors[i].numel >= 0, "adamw_step_ema: negative size");
+        MC_CHECK(tensors[i].numel == 0 || shadows[i], "adamw_step_ema: null shadow pointer");
+    }
+    const EmaHost ema{shadows, decay, warmup != 0, count};
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, &ema, stream);
+}
+
+extern "C" int mc_ema_update(float* const* shadows, const float* const* sources, const long long* numel, int n_tensors, double decay,
+                             int warmup, const long long* count, const float* found_inf, void* stream) {
+    MC_CHECK(n_tensors >= 0 && ((shadows && sources && numel) || n_tensors == 0), "ema_update: bad tensor lists");
+    MC_CHECK(ema_decay_ok(decay), "ema_update: decay must lie strictly between 0 and 1");
+    MC_CHECK(count, "ema_update: null update count");
+    for (int i = 0; i < n_tensors; ++i) {                       // every argument is checked before the first launch
+        MC_CHECK(numel[i] >= 0, "ema_update: negative size");
+        MC_CHECK(numel[i] == 0 || (shadows[i] && sources[i]), "ema_update: null tensor pointer");
+        MC_CHECK((numel[i] + CHUNK - 1) / CHUNK < (1ll << 30), "ema_update: tensor too large");
+    }
+    EmaPack pk;
+    int cnt = 0, chunks = 0;
+    auto flush = [&]() -> int {
+        if (cnt == 0) return MC_OK;
+        pk.first_chunk[cnt] = chunks;
+        hipLaunchKernelGGL(ema_multi_k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, count, decay, warmup != 0, found_inf);
+        MC_LAUNCH_CHECK();
+        cnt = 0; chunks = 0;
+        return MC_OK;
+    };
+    for (int i = 0; i < n_tensors; ++i) {
+        if (numel[i] == 0) continue;
+        const long long nch = (numel[i] + CHUNK - 1) / CHUNK;
+        if (cnt == PACK || (long long)chunks + nch > (1ll << 30)) {
+            int r = flush();
+            if (r != MC_OK) return r;
+        }
+        pk.e[cnt] = shadows[i]; pk.p[cnt] = sources[i]; pk.n[cnt] = numel[i]; pk.first_chunk[cnt] = chunks;
+        chunks += (int)nch;
+        ++cnt;
+    }
+    return flush();
+}
+
+extern "C" int mc_ema_tick(long long* count, const float* found_inf, void* stream) {
+    MC_CHECK(count, "ema_tick: null update count");
+    hipLaunchKernelGGL(ema_tick_k, dim3(1), dim3(64), 0, (hipStream_t)stream, count, found_inf);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
 }
 
 namespace {
 int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
-               long long step, const float* grad_coef, const float* found_inf, const float* skipped, void* stream) {
+               long long step, const float* grad_coef, const float* found_inf, const float* skipped, const EmaHost* ema, void* stream) {
     MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0), "adamw: bad tensor list");
     MC_CHECK(step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adamw: bad hyper-parameters");
     // scalars are derived in double like torch does on the host (1 - 0.999 in fp32 is already 1.3e-5 off)
@@ -435,11 +614,18 @@ int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double 
     ls.found_inf = found_inf; ls.skipped = skipped; ls.lr = lr; ls.beta1 = beta1; ls.beta2 = beta2; ls.step = step;
     ls.grad_coef = grad_coef;
     AdamPack pk;
+    AdamEma em;
+    if (ema) { em.count = ema->count; em.decay = ema->decay; em.warmup = ema->warmup; }
     int cnt = 0, chunks = 0;
     auto flush = [&]() -> int {
         if (cnt == 0) return MC_OK;
         pk.first_chunk[cnt] = chunks;
-        hipLaunchKernelGGL(grad_coef ? adamw_multi_k<true> : adamw_multi_k<false>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, s, ls);
+        if (ema)
+            hipLaunchKernelGGL((grad_coef ? adamw_multi_k<true, true> : adamw_multi_k<false, true>), dim3(chunks), dim3(256), 0,
+                               (hipStream_t)stream, pk, cnt, s, ls, em);
+        else
+            hipLaunchKernelGGL((grad_coef ? adamw_multi_k<true, false> : adamw_multi_k<false, false>), dim3(chunks), dim3(256), 0,
+                               (hipStream_t)stream, pk, cnt, s, ls, NoEma{});
         MC_LAUNCH_CHECK();
         cnt = 0; chunks = 0;
         return MC_OK;
@@ -456,6 +642,7 @@ int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double 
         }
         pk.p[cnt] = t.param; pk.g[cnt] = t.grad; pk.m[cnt] = t.exp_avg; pk.v[cnt] = t.exp_avg_sq;
         pk.img[cnt] = t.bf16_image;
+        if (ema) em.e[cnt] = ema->shadows[i];
         pk.n[cnt] = t.numel; pk.first_chunk[cnt] = chunks;
         chunks += (int)nch;
         ++cnt;

@@ -18,6 +18,7 @@ import torch.distributed as dist
 
 from . import lib as L
 from . import ops
+from .ema import ModelEma
 from .breastclip.model.modules import efficientnet_custom as _encmod
 
 
@@ -208,7 +209,8 @@ class LossScaler:
 class Trainer:
     def __init__(self, model, loss_func, optimizer, scheduler=None, device=None, bucket_mb: int = 256,
                  overlap_micro: bool = False, keep_graphs: int = 1, grad_sink: bool = True, keep_recompute: Optional[int] = None,
-                 stat_tapes: bool = True, loss_scale="auto", max_grad_norm: Optional[float] = None, deterministic: bool = False):
+                 stat_tapes: bool = True, loss_scale="auto", max_grad_norm: Optional[float] = None, deterministic: bool = False,
+                 ema=None):
         self.model, self.loss_func, self.optimizer, self.scheduler = model, loss_func, optimizer, scheduler
         # deterministic = True: ops.set_deterministic(True) for the duration of every step() (restored afterwards, also when the
         # step raises): the backward runs without float atomics and two steps from the same state give the same bits.  Single
@@ -257,6 +259,13 @@ class Trainer:
             # identical replicas: rank 0's parameters and buffers everywhere, like torch DDP does at construction
             # [ref: trainer_ddp.py:134] -- only gradients are averaged afterwards
             sync_parameters_and_buffers(model)
+        # weight EMA (ema.ModelEma): None = off (nothing changes by a bit); a number = that decay, with warm-up; or a ModelEma
+        # of this model.  Shadows are per rank: every rank averages the same weights, no collective is involved.
+        if ema is not None and not isinstance(ema, ModelEma):
+            ema = ModelEma(model, decay=float(ema))
+        elif ema is not None:
+            ema.bind(model)                     # (one that was built from another instance of the model, e.g. on a resume)
+        self.ema = ema
 
     def step(self, batch: Dict, micro_batches: int = 1) -> Dict[str, torch.Tensor]:
         prev = ops.set_deterministic(True) if self.deterministic else None
@@ -306,22 +315,28 @@ class Trainer:
         optimizer is the HIP AdamW (the kernel reads the flag); any other optimizer: one flag read per step.
         With ``max_grad_norm``: the global norm of the unscaled gradients and the clip coefficient are formed on the device
         (by the unscale pass itself under a scaler); the HIP AdamW multiplies by the coefficient as it loads the gradients
-        (``p.grad`` stays unclipped), any other optimizer has its gradients scaled in place first."""
+        (``p.grad`` stays unclipped), any other optimizer has its gradients scaled in place first.
+        With ``ema``: the shadows follow the applied step -- inside the HIP AdamW's pass for the parameters it updates, by
+        ``ModelEma.update`` for the rest -- and stay as they are on a skipped one; then the scaler update."""
         clip = self.max_grad_norm
+        ema = self.ema
+        hip_adamw = hasattr(self.optimizer, "step_loss_scaled")
+        kw = {"ema": ema} if ema is not None and hip_adamw else {}      # the HIP AdamW folds the shadows into its own pass
         if self.scaler is None and clip is None:
-            self.optimizer.step()
+            self.optimizer.step(**kw)
+            self._ema_rest()
             return
         params = list(self.model.parameters())
-        hip_adamw = hasattr(self.optimizer, "step_loss_scaled")
         if self.scaler is None:
             nc = self._norm_coef = ops.grad_norm_coef(params, clip, who="Trainer")
             if nc is None:                                  # (no parameter has a gradient)
-                self.optimizer.step()
+                self.optimizer.step(**kw)
             elif hip_adamw:
-                self.optimizer.step(grad_coef=nc[1:])
+                self.optimizer.step(grad_coef=nc[1:], **kw)
             else:
                 ops.grads_scale_(params, nc[1:])
                 self.optimizer.step()
+            self._ema_rest()
             return
         nc = None
         if hip_adamw:
@@ -329,7 +344,10 @@ class Trainer:
                 self.scaler.unscale_(params)
             else:
                 nc = self.scaler.unscale_(params, clip=clip)[1]
-            opt_skipped = self.optimizer.step_loss_scaled(self.scaler, grad_coef=None if nc is None else nc[1:])
+            opt_skipped = self.optimizer.step_loss_scaled(self.scaler, grad_coef=None if nc is None else nc[1:], **kw)
+            if ema is not None:                             # reads the flag on the device: before update() clears it
+                st = self.scaler.state(params[0].device)
+                self._ema_rest(st[LossScaler._FLAG:LossScaler._FLAG + 1])
             self.scaler.update(opt_skipped)
         else:
             if clip is None:
@@ -340,11 +358,18 @@ class Trainer:
                 if nc is not None:
                     ops.grads_scale_(params, nc[1:])
                 self.optimizer.step()
+                self._ema_rest()                            # (a step skipped on the host's reading of the flag: no update)
             self.scaler.update()
         self._norm_coef = nc
         self._steps_done = getattr(self, "_steps_done", 0) + 1
         if self._steps_done % self.scaler_check_every == 0:
             self.scaler.check()
+
+    def _ema_rest(self, found_inf=None):
+        """after the optimizer step: the shadows its pass did not move (buffers, parameters without a gradient; everything
+        under an optimizer other than the HIP AdamW), then the count of applied updates"""
+        if self.ema is not None:
+            self.ema.update(self.model, found_inf=found_inf)
 
     def _result(self, loss_dict):
         out = {k: v.detach() for k, v in loss_dict.items()}

@@ -108,6 +108,9 @@ _SIGS = {
     "mc_grads_unscale_norm_dev": ([C.POINTER(AdamwTensor), I, P, P, P, LL, F, P, P], I),
     "mc_grads_scale_dev": ([C.POINTER(AdamwTensor), I, P, P], I),
     "mc_adamw_step_clip": ([C.POINTER(AdamwTensor), I, D, D, D, D, D, LL, P, P, P, P], I),
+    "mc_adamw_step_ema": ([C.POINTER(AdamwTensor), P, I, D, D, D, D, D, LL, D, I, P, P, P, P, P], I),
+    "mc_ema_update": ([P, P, P, I, D, I, P, P, P], I),
+    "mc_ema_tick": ([P, P, P], I),
     "mc_gemm_bf16": ([C.POINTER(GemmArgs), P], I),
     "mc_gemm_stat_rows": ([C.POINTER(GemmArgs)], I),
     "mc_gemm_tile_config": ([C.POINTER(GemmArgs)], I),
