@@ -86,7 +86,9 @@ typedef struct mc_gemm_args {
      * efficientnet_custom.py:104,122,283): A and B hold OCP e4m3 bytes (gfx950's fp8, NOT the fnuz form), lda / ldb /
      * strides in elements (= bytes), K, lda, ldb multiples of 16; plain NT layout, bf16 output, fp32 accumulation
      * (v_mfma_f32_16x16x32_fp8_fp8).  The product of the two per-tensor dequantisation scales is passed in alpha and/or
-     * alpha_dev (device scalar, multiplied onto alpha; produced by mc_quant_fp8_bf16 without a host round trip). */
+     * alpha_dev (device scalar, multiplied onto alpha; produced by mc_quant_fp8_bf16 without a host round trip).
+     * alpha_dev is read by the 256 x 256 NT kernel of gemm256.hip only (with or without ab_fp8): a problem that carries it
+     * and is not served by that kernel -- any other layout, fp32 output, the TN weight-gradient kernel -- is an error. */
     int ab_fp8;
     const float* alpha_dev;
 } mc_gemm_args;
@@ -108,7 +110,10 @@ int mc_gemm256_tn_splits(long long m, long long n, long long k, long long group_
  * mc_amax_bf16:       amax[0] = max(amax[0], max |x|)   (caller zero-fills amax; integer atomic, deterministic)
  * mc_quant_fp8_bf16:  y = e4m3(clamp(x * 448 / amax_in[0], +-448));  scale_out[0] = amax_in[0] / 448 (the dequantisation
  *                     scale, optional);  amax_next[0] = max(amax_next[0], max |x|) (optional: delayed scaling measures the
- *                     tensor it converts);  n % 8 == 0, contiguous. */
+ *                     tensor it converts);  n % 8 == 0, contiguous.
+ *                     The scale is finite for every finite amax_in > 0 (below 2^-100 amax and x are both multiplied by 2^64
+ *                     before the division, which changes no rounding): finite x never gives a NaN code, +-amax gives +-448.
+ *                     amax_in = 0 -> scale 1 and scale_out 1;  NaN amax_in or NaN x -> NaN code (0x7f / 0xff). */
 int mc_amax_bf16(const mc_bf16* x, long long n, float* amax, void* stream);
 int mc_quant_fp8_bf16(const mc_bf16* x, long long n, const float* amax_in, unsigned char* y, float* scale_out,
                       float* amax_next, void* stream);

@@ -3,6 +3,13 @@
 //   scale  = 448 / amax           (448 = largest finite e4m3 value; gfx950 implements the OCP format, not fnuz)
 //   q      = e4m3(clamp(x * scale, -448, 448))        v_cvt_pk_fp8_f32, round to nearest even
 //   x      ~ q * (amax / 448)
+// The scale stays finite for every finite amax > 0: 448 / amax overflows fp32 below 448 / FLT_MAX (~1.3e-36, a value bf16
+// holds; a stale delayed-scaling amax or an all-tiny tensor gets there), and with scale = +inf every zero of the tensor
+// would become 0 * inf = NaN (code 0x7f).  For 0 < amax < 2^-100 both amax and x are multiplied by 2^64 first:
+//   scale = 448 / (amax * pre),  q = e4m3(clamp((x * pre) * scale)),  pre = 2^64 (else 1: the products above, bit for bit)
+// pre is a power of two, so no rounding changes: the codes are those of fp32 with an unbounded exponent (x = +-amax gives
+// +-448, zeros stay zeros, x * pre beyond FLT_MAX saturates like any |x| > amax).  A finite input under a finite positive
+// amax never produces a NaN code.  amax = 0 -> scale 1; a NaN amax -> every code NaN (see nmax below).
 // amax comes from the caller: either measured on this tensor first (mc_amax_bf16, "current scaling") or carried over from
 // the previous step (delayed scaling: the quantisation pass also measures the amax of the tensor it converts).
 // HBM-bound streaming kernels: 16-byte loads, 8-byte stores, one integer atomic per workgroup for the amax
@@ -41,7 +48,8 @@ __global__ __launch_bounds__(256) void quant_fp8_bf16_k(const bf16_t* __restrict
                                                         unsigned char* __restrict__ y, float* __restrict__ scale_out,
                                                         unsigned* __restrict__ amax_next) {
     const float amax = amax_in[0];
-    const float scale = amax != amax ? amax : (amax > 0.f ? 448.0f / amax : 1.0f);
+    const float pre = (amax > 0.f && amax < 0x1p-100f) ? 0x1p64f : 1.0f;      // keeps the scale finite (header comment)
+    const float scale = amax != amax ? amax : (amax > 0.f ? 448.0f / (amax * pre) : 1.0f);
     if (blockIdx.x == 0 && threadIdx.x == 0 && scale_out) scale_out[0] = amax > 0.f ? amax / 448.0f : 1.0f;
     float m = 0.f;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
@@ -50,7 +58,7 @@ __global__ __launch_bounds__(256) void quant_fp8_bf16_k(const bf16_t* __restrict
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             m = nmax(fabsf(f[q]), m);
-            const float v = f[q] * scale;
+            const float v = (f[q] * pre) * scale;
             f[q] = v != v ? v : fminf(fmaxf(v, -448.0f), 448.0f);          // clamp finite values, let NaN through
         }
         int lo = 0, hi = 0;

@@ -289,7 +289,7 @@ extern "C" int mc_gemm256_tn_eligible(const mc_gemm_args* a) {
     const mc_gemm_args& p = *a;
     const int mode = g8t_mode();
     if (mode == 0) return 0;
-    if (!p.a_kmajor || !p.b_kmajor || !p.c_f32 || p.pro_operand != 0 || p.nb2 > 1 || p.batch > 1 || p.ab_fp8 || p.bias || p.R) return 0;
+    if (!p.a_kmajor || !p.b_kmajor || !p.c_f32 || p.pro_operand != 0 || p.nb2 > 1 || p.batch > 1 || p.ab_fp8 || p.alpha_dev || p.bias || p.R) return 0;
     if (p.alpha != 0.f && p.alpha != 1.f) return 0;
     if (p.splits > 1 && !p.splitk_ws) return 0;
     if (p.splits <= 1 && p.c_atomic) return 0;
