@@ -895,6 +895,30 @@ int mc_adamw_step_ema(const mc_adamw_tensor* tensors, float* const* shadows, int
 int mc_ema_update(float* const* shadows, const float* const* sources, const long long* numel, int n_tensors, double decay,
                   int warmup, const long long* count, const float* found_inf, void* stream);
 int mc_ema_tick(long long* count, const float* found_inf, void* stream);
+/* SGD with momentum, the other optimizer of the reference's factory [ref: breastclip/optimizer/__init__.py:26-27 ->
+ * torch.optim.SGD(model.parameters(), **config)].  Multi-tensor, in place, fp32, packed like mc_adamw_step; `tensors` is the same
+ * HOST table: exp_avg carries the momentum buffer (NULL allowed when momentum == 0), exp_avg_sq is not read, bf16_image keeps
+ * its meaning.  RULE, per element, every operation rounded to fp32 on its own and never fused (what separate tensor operations
+ * of torch give on any IEEE host):
+ *   g' = maximize ? -g : g
+ *   g' = g' * c                                   only with grad_coef (c = *grad_coef, a device scalar; grad is not rewritten)
+ *   g' = g' + wd * p                              only if weight_decay != 0
+ *   momentum != 0:  buf = g'                                          on the first APPLIED step of the launch set
+ *                   buf = mu * buf + (1 - dampening) * g'             otherwise
+ *                   d = nesterov ? g' + mu * buf : buf
+ *   momentum == 0:  d = g'                        (no buffer is read or written)
+ *   p = p - lr * d
+ * lr, mu, 1 - dampening (formed in double) and wd are rounded to fp32 once, on the host.  `step` >= 1 is the host's count for
+ * the launch set: without a loss scale the first applied step is step == 1; with one (found_inf / skipped both set) it is
+ * step - *skipped <= 1, read on the device, and *found_inf != 0 makes the whole call a no-op -- a skipped first step leaves the
+ * buffer unwritten and the next applied step sets buf = g'.  `shadows` (optional, a HOST array parallel to `tensors`) folds the
+ * weight EMA of mc_ema_update into the pass, applied to the updated p with w from *count exactly as there; decay, warmup and
+ * count are ignored when shadows is NULL.  Every argument is checked before the first launch: NULL list, negative size, NULL
+ * pointers of non-empty tensors, NULL shadow, half-set loss-scale pair, nesterov without momentum or with dampening, negative
+ * lr / momentum / weight_decay, step < 1, decay outside (0, 1), NULL count. */
+int mc_sgd_step(const mc_adamw_tensor* tensors, float* const* shadows, int n_tensors, double lr, double momentum, double dampening,
+                double weight_decay, int nesterov, int maximize, long long step, double decay, int warmup, const long long* count,
+                const float* grad_coef, const float* found_inf, const float* skipped, void* stream);
 
 #ifdef __cplusplus
 }

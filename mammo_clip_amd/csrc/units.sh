@@ -1,6 +1,6 @@
 # The translation units of the kernel library, their compile flags and their staleness rule.  Sourced (not run) by
 # csrc/build.sh and scripts/ab_variant.sh, with $CSRC = this directory: a library either of them links holds the same units.
-SRCS="gemm gemm256 gemm256_tn fp8 gemm_rows gemm_wgrad_rows conv conv_lane bnact bnfold bert attn head retrieval augment optim util stem"
+SRCS="gemm gemm256 gemm256_tn fp8 gemm_rows gemm_wgrad_rows conv conv_lane bnact bnfold bert attn head retrieval augment optim optim_sgd util stem"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result"
 unit_headers() {      # $1 = unit: the headers its object depends on
   case $1 in

@@ -12,8 +12,8 @@ shadow and does not advance ``k``: the count is a device integer this object own
 last one-thread launch advances it unless the scaler's non-finite flag is set -- so an update has to be complete before
 ``LossScaler.update`` clears that flag.  The host reads the count only when asked (``updates``, ``state_dict()``).
 
-Two routes, one arithmetic: ``AdamW.step(ema=)`` / ``step_loss_scaled(ema=)`` fold the shadows of the parameters they update
-into the optimizer pass itself (``mc_adamw_step_ema``: the updated parameter is still in registers) and ``update(model)``
+Two routes, one arithmetic: ``AdamW.step(ema=)`` / ``step_loss_scaled(ema=)`` (and ``SGD``'s) fold the shadows of the parameters they
+update into the optimizer pass itself (``mc_adamw_step_ema``, ``mc_sgd_step``: the updated parameter is still in registers) and ``update(model)``
 does the rest -- buffers, parameters the pass did not cover, everything under another optimizer (``mc_ema_update``) -- then
 advances the count (``mc_ema_tick``).  There is no CPU fallback: on CPU tensors ``update`` raises, as ``AdamW`` does."""
 import copy

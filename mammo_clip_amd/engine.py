@@ -312,16 +312,16 @@ class Trainer:
     def _optimizer_step(self):
         """optimizer update; under a loss scale: unscale the (already rank-averaged) gradients first and skip the update
         if any of them is non-finite, like GradScaler.step() [ref: trainer_ddp.py:300-303] -- without a host sync when the
-        optimizer is the HIP AdamW (the kernel reads the flag); any other optimizer: one flag read per step.
+        optimizer is one of the HIP optimizers, AdamW or SGD (the kernel reads the flag); any other optimizer: one flag read per step.
         With ``max_grad_norm``: the global norm of the unscaled gradients and the clip coefficient are formed on the device
-        (by the unscale pass itself under a scaler); the HIP AdamW multiplies by the coefficient as it loads the gradients
+        (by the unscale pass itself under a scaler); a HIP optimizer multiplies by the coefficient as it loads the gradients
         (``p.grad`` stays unclipped), any other optimizer has its gradients scaled in place first.
-        With ``ema``: the shadows follow the applied step -- inside the HIP AdamW's pass for the parameters it updates, by
+        With ``ema``: the shadows follow the applied step -- inside a HIP optimizer's pass for the parameters it updates, by
         ``ModelEma.update`` for the rest -- and stay as they are on a skipped one; then the scaler update."""
         clip = self.max_grad_norm
         ema = self.ema
-        hip_adamw = hasattr(self.optimizer, "step_loss_scaled")
-        kw = {"ema": ema} if ema is not None and hip_adamw else {}      # the HIP AdamW folds the shadows into its own pass
+        hip_opt = hasattr(self.optimizer, "step_loss_scaled")
+        kw = {"ema": ema} if ema is not None and hip_opt else {}      # AdamW / SGD fold the shadows into their own pass
         if self.scaler is None and clip is None:
             self.optimizer.step(**kw)
             self._ema_rest()
@@ -331,7 +331,7 @@ class Trainer:
             nc = self._norm_coef = ops.grad_norm_coef(params, clip, who="Trainer")
             if nc is None:                                  # (no parameter has a gradient)
                 self.optimizer.step(**kw)
-            elif hip_adamw:
+            elif hip_opt:
                 self.optimizer.step(grad_coef=nc[1:], **kw)
             else:
                 ops.grads_scale_(params, nc[1:])
@@ -339,7 +339,7 @@ class Trainer:
             self._ema_rest()
             return
         nc = None
-        if hip_adamw:
+        if hip_opt:
             if clip is None:
                 self.scaler.unscale_(params)
             else:
@@ -367,7 +367,7 @@ class Trainer:
 
     def _ema_rest(self, found_inf=None):
         """after the optimizer step: the shadows its pass did not move (buffers, parameters without a gradient; everything
-        under an optimizer other than the HIP AdamW), then the count of applied updates"""
+        under an optimizer other than the HIP AdamW / SGD), then the count of applied updates"""
         if self.ema is not None:
             self.ema.update(self.model, found_inf=found_inf)
 

@@ -111,6 +111,7 @@ _SIGS = {
     "mc_adamw_step_ema": ([C.POINTER(AdamwTensor), P, I, D, D, D, D, D, LL, D, I, P, P, P, P, P], I),
     "mc_ema_update": ([P, P, P, I, D, I, P, P, P], I),
     "mc_ema_tick": ([P, P, P], I),
+    "mc_sgd_step": ([C.POINTER(AdamwTensor), P, I, D, D, D, D, I, I, LL, D, I, P, P, P, P, P], I),
     "mc_gemm_bf16": ([C.POINTER(GemmArgs), P], I),
     "mc_gemm_stat_rows": ([C.POINTER(GemmArgs)], I),
     "mc_gemm_tile_config": ([C.POINTER(GemmArgs)], I),
