@@ -424,11 +424,13 @@ __global__ __launch_bounds__(256) void softmax_fwd_k(const float* __restrict__ s
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += (long long)gridDim.x * 4) {
         float v[MAXT];
-        float mx = -3.4e38f;
+        // the start of the maximum and the filler of the slots past t lie under every finite score: a row whose keys all carry
+        // mc_mask_bias's -FLT_MAX keeps its own maximum and comes out uniform (1/t), as from torch and softmax_fwd_v8_k
+        float mx = -INFINITY;
 #pragma unroll
         for (int i = 0; i < MAXT; ++i) {
             int k = lane + i * 64;
-            v[i] = (k < t) ? sc[row * t + k] : -3.4e38f;
+            v[i] = (k < t) ? sc[row * t + k] : -INFINITY;
             mx = fmaxf(mx, v[i]);
         }
         mx = wave_max(mx);
