@@ -783,6 +783,28 @@ int mc_cls_record(const float* score, const int* label, const unsigned int* coun
  * [ref: evaluator.py:341-344 (pr_auc(get_all=True): precision = tp/(tp+fp), recall = tp/n_pos, finished by the caller)] */
 int mc_cls_curve(const float* score, const unsigned int* counts, int N, int K, unsigned int* pos_ws, int* tp, int* fp,
                  float* threshold, void* stream);
+/* B bootstrap replicates of the record: records [B][20], replicate r = mc_cls_record's 20 slots on the
+ * multiset of N samples drawn with replacement (NaN and label counters 0; K = the distinct scores present; a score absent
+ * from a replicate is no threshold of it).  Draw t of replicate r takes sample (u N) >> 32 with u = word t & 3 of
+ * philox4x32(t >> 2, r, 0x626f6f74, 0x5bd1e995; key seed low, seed high) -- a function of (seed, r, t, N) only, never of
+ * the scores.  stratified != 0: draws t < n_pos take the ((u n_pos) >> 32)-th positive in index order, the others the
+ * ((u n_neg) >> 32)-th negative, so every replicate keeps the class counts.  counts: what mc_rank_counts wrote for these
+ * scores and labels; bin = N - pos_ge - neg_ge orders the thresholds, so no sort runs (a sample the counts do not place, e.g.
+ * a NaN score, is folded into the highest bin: check the point record's counters first).  A replicate is a histogram
+ * [bin][class] filled by integer atomics, then one workgroup scans it from the highest bin down: gt, eq and the threshold's
+ * four in integers, the best-pF1 candidate by mc_cls_record's exact order, the fp64 sums per thread in scan order and over
+ * the threads in a fixed tree.  No float atomics; the same bits on every call, on any stream and for any chunk size.
+ * 1 <= N <= 2^24, 1 <= B <= 2^20.  ws: ws_bytes >= mc_boot_ws_bytes(N, B) bytes (0 for arguments out of range), 16-byte
+ * aligned: the tables (16 N bytes) plus the histograms of one chunk of replicates (8 N bytes each, about 64 MiB per chunk). */
+long long mc_boot_ws_bytes(int N, int B);
+int mc_boot_records(const float* score, const int* label, const unsigned int* counts, int N, int B, double threshold,
+                    unsigned long long seed, int stratified, long long* records, void* ws, long long ws_bytes, void* stream);
+/* replicates per chunk of mc_boot_records: 0 = chosen per call (64 MiB of histograms), 1..65535 = fixed (capped at B);
+ * mc_boot_ws_bytes follows it and the records do not depend on it.  Process-wide developer / test switch. */
+int mc_boot_set_chunk(int chunk);
+/* which stages mc_boot_records launches: bit 0 the tables and the histograms, bit 1 the record scan; 3 (the default) is the
+ * op, 1 and 2 exist to time each kernel on its own (scripts/boot_metrics_bench.py).  Process-wide developer switch. */
+int mc_boot_set_stages(int mask);
 
 /* ------------------------------------------------------------------------------------------------
  * training augmentation (augment.hip): flips, affine and elastic warp of the reference's train transform as one gather per

@@ -9,9 +9,30 @@ numpy on the host.  The module-level ``pfbeta`` / ``pfbeta_binarized`` / ``auroc
 through the rank-count kernels of csrc/retrieval.hip and one small record is read back, numpy arrays through a sort on the
 host.  No sklearn / scipy anywhere.
 
-Out of scope: tokenising prompts, datasets and loaders, bootstrap confidence intervals, sharding one evaluation over several
-ranks, and any change to ``engine.validate``."""
+Bootstrap confidence intervals (``bootstrap_metrics`` / ``bootstrap_compare`` / ``zeroshot_metrics(detail=True, n_boot=B)``;
+DESIGN.md section 9q).  The specification both paths follow:
+
+* Replicate ``r`` (0 <= r < B) is N draws ``t`` (0 <= t < N).  Draw ``t`` picks sample ``idx = (u * N) >> 32`` where ``u`` is
+  word ``t & 3`` of ``philox4x32(t >> 2, r, 0x626f6f74, 0x5bd1e995; key = (seed & 0xffffffff, seed >> 32))`` -- the
+  function of csrc/common_hip.h and mammo_clip_amd/augment.py.  The index is a function of (seed, r, t, N) and never of the
+  scores: two score vectors bootstrapped with the same seed see the same resamples (``bootstrap_compare`` rests on this).
+  The multiply-high map is not exactly uniform: index probabilities differ by at most N / 2^32 relative.
+* ``stratified=True``: draws ``t < n_pos`` pick ``pos[(u * n_pos) >> 32]`` from the positives in index order, the other
+  ``n_neg`` draws ``neg[(u * n_neg) >> 32]`` from the negatives: every replicate keeps the class counts.
+* One replicate's result is the 20-slot record of ``ops.cls_record`` on the resampled multiset: the same integer slots
+  (``n_pos``, ``n_neg``, ``gt``, ``eq``, the best-pF1 ``(tp, fp, threshold bits)``, the four counts at ``threshold``, ``k`` =
+  the distinct scores present; NaN and label counters 0) and the same fp64 slots (PR-AUC, AP, the two clip sums).  A score
+  absent from a replicate is no threshold of it; the start point (0, 0) has precision 1; without a positive PR-AUC and AP are
+  NaN and the best candidate is (0, 0, -inf).  Both paths form it from ``bin(i)`` = the number of samples with a strictly
+  smaller score (tied samples share a bin, bins ascend with the score): a replicate is a histogram over (bin, class), scanned
+  from the highest bin down.  The host finishes every replicate with ``_metrics_of_record``.
+* Per key: ``lo, hi = np.nanquantile(values, [alpha / 2, 1 - alpha / 2])``, ``se = np.nanstd(values, ddof=1)`` and
+  ``n_valid`` = the replicates where the key is not NaN.  B x 160 bytes leave the device.
+
+Out of scope: tokenising prompts, datasets and loaders, sharding one evaluation over several ranks, and any change to
+``engine.validate``."""
 import logging
+import warnings
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -141,7 +162,8 @@ class Evaluator:
         return np.take_along_axis(s, idx, axis=1), idx.astype(np.int32)
 
     @staticmethod
-    def zeroshot_metrics(image_embeddings, prompt_embeddings: Dict, labels: Dict, detail: bool = False) -> Dict:
+    def zeroshot_metrics(image_embeddings, prompt_embeddings: Dict, labels: Dict, detail: bool = False, n_boot: int = 0,
+                         seed: int = 0, stratified: bool = False, alpha: float = 0.05) -> Dict:
         """Zero-shot classification [ref: evaluator.py:160-190]: ``prompt_embeddings`` = ``{label_text: [M, D]}`` (the encoded
         prompts of one finding), ``labels`` = ``{"mass", "calc", "density", "cancer"}`` (whichever are present, one integer per
         image).  ``mass`` / ``suspicious_calcification`` / ``cancer`` / ``malignancy``: AUROC of the softmax's column 1
@@ -150,7 +172,13 @@ class Evaluator:
         roc_curve + auc; with one class only it is NaN.  Device tensors (unit-norm fp32 rows, as in ``retrieval_i2t``):
         ``mc_sim_softmax`` + ``mc_auroc_counts``.  ``detail=True``: every binary finding maps to its ``binary_metrics``
         dict (threshold 0.5) instead of the bare AUROC -- on the device ``mc_rank_counts`` + ``mc_cls_record``, one record read
-        per finding."""
+        per finding.  ``n_boot > 0`` (with ``detail=True``): every binary finding's dict gains ``"bootstrap"``, the
+        ``bootstrap_metrics`` dict of that finding (``seed``, ``stratified``, ``alpha`` as there; on the device
+        ``mc_boot_records``, n_boot more records read per finding)."""
+        if n_boot:
+            if not detail:
+                raise ValueError("zeroshot_metrics: n_boot > 0 needs detail=True")
+            _check_boot_args(n_boot, alpha)
         source = {"suspicious_calcification": "calc", "mass": "mass", "density": "density", "cancer": "cancer",
                   "malignancy": "cancer"}
         dev = _on_device(image_embeddings)
@@ -175,7 +203,9 @@ class Evaluator:
                     pending.append((label_text, None, (p.argmax(dim=1) == y).sum()))
                 elif detail:
                     col, y = _dev_score_label(y, p[:, 1])
-                    pending.append((label_text, ops.cls_record(col, y, ops.rank_counts(col, y)), None))
+                    counts = ops.rank_counts(col, y)
+                    boot = ops.boot_records(col, y, counts, n_boot, 0.5, seed, stratified) if n_boot else None
+                    pending.append((label_text, (ops.cls_record(col, y, counts), boot), None))
                 else:
                     pending.append((label_text, ops.auroc_counts(p[:, 1].contiguous(), y), None))
             else:
@@ -187,6 +217,8 @@ class Evaluator:
                     results[label_text] = float((p.argmax(axis=1) == y).sum()) / len(y)
                 elif detail:
                     results[label_text] = binary_metrics(y, p[:, 1])
+                    if n_boot:
+                        results[label_text]["bootstrap"] = bootstrap_metrics(y, p[:, 1], n_boot, 0.5, seed, stratified, alpha)
                 else:
                     pos, neg = p[y != 0, 1], np.sort(p[y == 0, 1])
                     lo, hi = np.searchsorted(neg, pos, side="left"), np.searchsorted(neg, pos, side="right")
@@ -197,7 +229,10 @@ class Evaluator:
             if counts is None:
                 results[label_text] = int(correct) / a.shape[0]
             elif detail:
-                results[label_text] = _metrics_of_record(_read_record(counts))
+                results[label_text] = _metrics_of_record(_read_record(counts[0]))
+                if n_boot:
+                    value = dict(results[label_text])
+                    results[label_text]["bootstrap"] = _boot_summary(value, counts[1].cpu().numpy(), alpha, False)
             else:
                 results[label_text] = _auroc(*[int(v) for v in counts.cpu()])
         return results
@@ -303,6 +338,159 @@ def binary_metrics(gt, pred, threshold=0.5) -> Dict:
                            ctp, cfp, n_neg - cfp, n_pos - ctp)
 
 
+# ------------------------------------------------------------------------------------------ bootstrap confidence intervals
+# The specification is in the module docstring.  Device tensors: csrc/retrieval.hip (mc_boot_records);
+# numpy arrays: host Philox, np.bincount, cumsum -- the same records, integer for integer.
+BOOT_STREAM = 0x626F6F74          # counter word 2 of every draw
+BOOT_MAX_N = 1 << 24
+_BOOT_BLOCK_WORDS = 1 << 22       # draws generated at once on the host path
+
+
+def bootstrap_indices(gt, n_boot, seed=0, stratified=False, first=0) -> np.ndarray:
+    """int64 [n_boot, N]: the sample every draw of replicates ``first .. first + n_boot`` picks (``gt`` gives N, and the
+    classes when ``stratified``).  The draw of the specification, on the host."""
+    from ..augment import philox4x32
+    y = np.asarray(gt.cpu() if torch.is_tensor(gt) else gt).reshape(-1) != 0
+    n, seed = len(y), int(seed) & 0xFFFFFFFFFFFFFFFF
+    q = np.arange((n + 3) >> 2, dtype=np.uint64)[None, :]
+    r = np.arange(first, first + n_boot, dtype=np.uint64)[:, None]
+    words = philox4x32(q, r, BOOT_STREAM, 0x5bd1e995, seed & 0xFFFFFFFF, seed >> 32)
+    u = np.stack(words, axis=2).reshape(n_boot, -1)[:, :n]                  # word t & 3 of counter t >> 2 at column t
+    s32 = np.uint64(32)
+    if not stratified:
+        return ((u * np.uint64(n)) >> s32).astype(np.int64)
+    pos, neg = np.flatnonzero(y), np.flatnonzero(~y)
+    idx = np.empty((n_boot, n), dtype=np.int64)
+    if len(pos):
+        idx[:, :len(pos)] = pos[((u[:, :len(pos)] * np.uint64(len(pos))) >> s32).astype(np.int64)]
+    if len(neg):
+        idx[:, len(pos):] = neg[((u[:, len(pos):] * np.uint64(len(neg))) >> s32).astype(np.int64)]
+    return idx
+
+
+def _host_boot_records(y, s, n_boot, threshold, seed, stratified) -> np.ndarray:
+    """int64 [n_boot, 20]: the records ``ops.boot_records`` returns, from the same bins and the same draws.  The best-pF1
+    candidate maximises tp / (tp + fp + n_pos) in fp64: two different such fractions (denominators below 2^26) are more than
+    2^-52 apart, so the fp64 order is the exact order; ``argmax`` keeps the first = the highest threshold on equal value."""
+    n = len(s)
+    bins = np.searchsorted(np.sort(s), s, side="left")                      # samples with a strictly smaller score
+    top = n - 1 - bins                                                      # position in descending order
+    sd = np.zeros(n, dtype=np.float64)
+    sd[top] = s                                                             # (tied samples store the same value)
+    pred = sd >= threshold
+    clip = np.clip(sd, 0.0, 1.0)
+    out = np.zeros((n_boot, 20), dtype=np.int64)
+    f64 = out[:, 16:].view(np.float64)
+    block = max(1, _BOOT_BLOCK_WORDS // n)
+    for r0 in range(0, n_boot, block):
+        idx = bootstrap_indices(y, min(block, n_boot - r0), seed, stratified, first=r0)
+        for k, row in enumerate(idx):
+            yy, tt = y[row], top[row]
+            cp, cn = np.bincount(tt[yy], minlength=n), np.bincount(tt[~yy], minlength=n)
+            tp1, fp1 = np.cumsum(cp), np.cumsum(cn)
+            tp0, fp0 = tp1 - cp, fp1 - cn
+            n_pos, n_neg = int(tp1[-1]), int(fp1[-1])
+            rec, fr = out[r0 + k], f64[r0 + k]
+            rec[0], rec[1], rec[2], rec[3] = n_pos, n_neg, int(np.sum(cn * tp0)), int(np.sum(cp * cn))
+            rec[4], rec[5], rec[6] = 0, 0, 0xFF800000                       # no candidate: (0, 0, -inf)
+            rec[7], rec[8] = int(cp[pred].sum()), int(cn[pred].sum())
+            rec[9], rec[10] = n_neg - rec[8], n_pos - rec[7]
+            here = np.flatnonzero(cp + cn)
+            rec[11] = len(here)
+            fr[0] = fr[1] = _NAN
+            fr[2], fr[3] = float(np.sum(clip * cp)), float(np.sum(clip * cn))
+            if n_pos == 0:
+                continue
+            cand = np.flatnonzero(cp)
+            j = cand[np.argmax(tp1[cand] / (tp1[cand] + fp1[cand] + np.float64(n_pos)))]
+            rec[4], rec[5] = tp1[j], fp1[j]
+            rec[6] = int(np.array([sd[j]], dtype=np.float32).view(np.uint32)[0])
+            a1, b1, a0, b0 = (v[here].astype(np.float64) for v in (tp1, fp1, tp0, fp0))
+            p1 = a1 / (a1 + b1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                p0 = np.where(a0 + b0 > 0, a0 / (a0 + b0), 1.0)             # the curve's start: precision 1
+            dr = a1 / np.float64(n_pos) - a0 / np.float64(n_pos)
+            fr[0], fr[1] = float(np.sum(dr * (p1 + p0) / 2.0)), float(np.sum(dr * p1))
+    return out
+
+
+def _check_boot_args(n_boot, alpha, n=None):
+    if int(n_boot) != n_boot or n_boot < 1 or n_boot > 1 << 20:
+        raise ValueError(f"bootstrap: n_boot must be an integer in [1, 2^20], got {n_boot}")
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"bootstrap: alpha must lie inside (0, 1), got {alpha}")
+    if n is not None and not 1 <= n <= BOOT_MAX_N:
+        raise ValueError(f"bootstrap: the number of samples must lie in [1, 2^24], got {n}")
+
+
+def _boot_summary(value: Dict, records, alpha, get_all) -> Dict:
+    """{key: {"value", "lo", "hi", "se", "n_valid"[, "replicates"]}} from the point estimates and the int64 [B, 20] records"""
+    reps = [_metrics_of_record(_record_of_raw(row)) for row in records]
+    out = {}
+    for key in BINARY_KEYS:
+        out[key] = _interval(value[key], np.asarray([m[key] for m in reps], dtype=np.float64), alpha, get_all)
+    return out
+
+
+def _interval(value, vals, alpha, get_all) -> Dict:
+    n_valid = int(np.count_nonzero(~np.isnan(vals)))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)                     # all-NaN keys and ddof=1 of one value give NaN
+        lo, hi = np.nanquantile(vals, [alpha / 2.0, 1.0 - alpha / 2.0])
+        se = np.nanstd(vals, ddof=1)
+    res = {"value": value, "lo": float(lo), "hi": float(hi), "se": float(se), "n_valid": n_valid}
+    if get_all:
+        res["replicates"] = vals
+    return res
+
+
+def _numel(x) -> int:
+    return int(x.numel()) if torch.is_tensor(x) else int(np.asarray(x).size)
+
+
+def bootstrap_metrics(gt, pred, n_boot=1000, threshold=0.5, seed=0, stratified=False, alpha=0.05, get_all=False) -> Dict:
+    """Percentile bootstrap of ``binary_metrics``: ``{key: {"value", "lo", "hi", "se", "n_valid"}}`` for the BINARY_KEYS.
+    ``value`` is the point estimate (that path runs first and raises its ValueErrors), ``lo`` / ``hi`` the ``alpha / 2`` and
+    ``1 - alpha / 2`` quantiles over ``n_boot`` replicates, ``se`` their standard deviation (ddof 1), ``n_valid`` the
+    replicates where the key is not NaN (the others are left out of the three).  ``get_all=True`` adds ``"replicates"``, the
+    fp64 [n_boot] values.  ``stratified``: every replicate keeps the class counts.  The resamples depend on ``seed`` (and N,
+    and the labels when stratified) only.  Device tensors: ``mc_rank_counts`` once, then ``mc_boot_records``; n_boot records
+    of 160 bytes are read back.  numpy arrays: the host path of the same specification, record for record."""
+    if _numel(gt) != _numel(pred):
+        raise ValueError("one label per score, and at least one score")
+    _check_boot_args(n_boot, alpha, _numel(pred))
+    if _on_device(pred):
+        from .. import ops
+        score, label = _dev_score_label(gt, pred)
+        counts = ops.rank_counts(score, label)
+        value = _metrics_of_record(_read_record(ops.cls_record(score, label, counts, threshold)))
+        records = ops.boot_records(score, label, counts, n_boot, threshold, seed, stratified).cpu().numpy()
+    else:
+        value = binary_metrics(gt, pred, threshold)
+        y, s = _host_score_label(gt, pred)
+        records = _host_boot_records(y, s, int(n_boot), threshold, seed, stratified)
+    return _boot_summary(value, records, alpha, get_all)
+
+
+def bootstrap_compare(gt, pred_a, pred_b, n_boot=1000, threshold=0.5, seed=0, stratified=False, alpha=0.05,
+                      get_all=False) -> Dict:
+    """Paired bootstrap of two score vectors on the same cases: both are resampled with the same seed, so replicate r holds
+    the same cases for both.  ``{key: {"value", "lo", "hi", "se", "n_valid", "p_le_0"}}`` of the difference ``a - b``:
+    ``value`` the difference of the point estimates, the interval and ``se`` over the replicates where both are defined
+    (``n_valid``), ``p_le_0`` the share of those with ``a - b <= 0`` (NaN without one)."""
+    if not _numel(gt) == _numel(pred_a) == _numel(pred_b):
+        raise ValueError("one label per score of either vector, and at least one score")
+    a = bootstrap_metrics(gt, pred_a, n_boot, threshold, seed, stratified, alpha, get_all=True)
+    b = bootstrap_metrics(gt, pred_b, n_boot, threshold, seed, stratified, alpha, get_all=True)
+    out = {}
+    for key in BINARY_KEYS:
+        diff = a[key]["replicates"] - b[key]["replicates"]
+        res = _interval(a[key]["value"] - b[key]["value"], diff, alpha, get_all)
+        res["p_le_0"] = float(np.count_nonzero(diff <= 0) / res["n_valid"]) if res["n_valid"] else _NAN
+        out[key] = res
+    return out
+
+
 def classification_score(result: Dict) -> Dict:
     """Averages the per-finding dicts of ``result`` (``{finding: binary_metrics(...)}``) into the reference's ``"...(Avg)"``
     keys, adds them to ``result`` and returns it [ref: evaluator.py:255-277]"""
@@ -368,12 +556,17 @@ def _metrics_of_record(rec: Dict) -> Dict:
 
 def _read_record(record) -> Dict:
     """the one host read of a device record (ops.cls_record); raises for what the device counted as unusable input"""
+    rec = _record_of_raw(record.cpu().numpy())
+    _raise_bad_input(rec["n_nan"], rec["n_bad_label"])
+    return rec
+
+
+def _record_of_raw(raw) -> Dict:
+    """int64 [20] (the layout of ops.cls_record) -> the record dict"""
     from .. import ops
-    raw = record.cpu().numpy()
     rec = {k: int(v) for k, v in zip(ops.CLS_RECORD_INTS, raw)}
     rec.update({k: float(v) for k, v in zip(ops.CLS_RECORD_F64, raw[16:].view(np.float64))})
     rec["best_threshold"] = float(np.array([raw[6] & 0xffffffff], dtype=np.uint32).view(np.float32)[0])
-    _raise_bad_input(rec["n_nan"], rec["n_bad_label"])
     return rec
 
 

@@ -1,6 +1,7 @@
 // Evaluation metrics on the device: image-to-report retrieval ranks, top-k retrieval, the zero-shot softmax and the pair
 // counts behind AUROC; per-sample rank counts and the record of binary-classification metrics (pF1, PR-AUC, AP, threshold
-// scores) reduced from them.  All fp32 (embeddings are fp32 in both storage builds).
+// scores) reduced from them, and the same record for every bootstrap replicate of the samples.  All
+// fp32 (embeddings are fp32 in both storage builds).
 // [ref: breastclip/evaluator.py:146-252 (eval_zeroshot, eval_img_text_retrieval), 255-346 (classification scores)]
 //
 // The similarity product a[N,D] . b[M,D]^T is STREAMED: a workgroup owns 64 image rows and a chunk of the M texts, walks the
@@ -563,9 +564,238 @@ __global__ __launch_bounds__(256) void cls_final_k(const u64* __restrict__ ws, i
     rec[REC_CLIP_NEG] = (u64)__double_as_longlong(ftot[3]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Bootstrap replicates of the record.  bin(i) = N - pos_ge_i - neg_ge_i = the number of samples with a
+// strictly smaller score: equal for tied samples, monotone in the score, so the N bins (empty ones where scores tie) are the
+// thresholds in ascending order and a replicate is a histogram hist[bin][class] of its N draws -- no sort, no second sweep.
+constexpr uint32_t BOOT_STREAM = 0x626f6f74u;   // counter word 2 of every draw ("boot")
+constexpr int BOOT_TILE = 1024;                 // bins of one scan step: 256 threads x 4
+constexpr long long BOOT_HIST_CAP = 64ll << 20; // bytes of histogram of one chunk of replicates (chosen chunk; at least 1)
+constexpr int BOOT_MAX_B = 1 << 20;
+constexpr int BOOT_MAX_CHUNK = 65535;           // replicates of a chunk = gridDim.y of the histogram kernel
+
+// exclusive prefix of v over the 256 threads (lane order, then wave order) and the block's total; s_w: 4 words of LDS
+__device__ __forceinline__ u64 block_excl_scan_u64(u64 v, u64* s_w, u64* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t lo = __shfl_up((uint32_t)incl, o, 64), hi = __shfl_up((uint32_t)(incl >> 32), o, 64);
+        if (lane >= o) incl += ((u64)hi << 32) | lo;
+    }
+    __syncthreads();                                            // (the previous step's reads of s_w are done)
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    u64 off = 0;
+    for (int w = 0; w < wave; ++w) off += s_w[w];
+    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return off + incl - v;
+}
+
+// table[i] = bin(i) | class(i) << 31, bin_score[bin(i)] = s_i (tied samples store the same value).  A sample the counts do
+// not place (a NaN score counts nowhere) goes to bin N - 1: whatever the input, every bin is inside [0, N).
+__global__ __launch_bounds__(256) void boot_table_k(const float* __restrict__ score, const int* __restrict__ label,
+                                                    const uint32_t* __restrict__ counts, int N, uint32_t* __restrict__ table,
+                                                    float* __restrict__ bin_score) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const uint32_t ge = counts[(long long)i * RC_COLS + 0] + counts[(long long)i * RC_COLS + 1];
+    const uint32_t bin = ge - 1u < (uint32_t)N ? (uint32_t)N - ge : (uint32_t)N - 1u;
+    table[i] = bin | (label[i] != 0 ? 0x80000000u : 0u);
+    bin_score[bin] = score[i];
+}
+
+// one workgroup: strat[0 .. n_pos) = the table entries of the positives in index order, strat[N .. N + n_neg) = those of the
+// negatives; hdr = (n_pos, n_neg).  A tile of 1024 samples per step, block scan with a carried prefix.
+__global__ __launch_bounds__(256) void boot_strat_k(const uint32_t* __restrict__ table, int N, uint32_t* __restrict__ strat,
+                                                    uint32_t* __restrict__ hdr) {
+    __shared__ u64 s_w[4];
+    u64 carry = 0;                                              // positives so far << 32 | negatives so far
+    for (int base = 0; base < N; base += BOOT_TILE) {
+        const int i0 = base + 4 * (int)threadIdx.x;
+        uint32_t e[4];
+        u64 v = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            e[q] = i0 + q < N ? table[i0 + q] : 0u;
+            if (i0 + q < N) v += e[q] >> 31 ? 1ull << 32 : 1ull;
+        }
+        u64 total;
+        const u64 ex = block_excl_scan_u64(v, s_w, &total) + carry;
+        uint32_t p = (uint32_t)(ex >> 32), n = (uint32_t)ex;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (i0 + q >= N) continue;
+            if (e[q] >> 31) strat[p++] = e[q];
+            else strat[(long long)N + n++] = e[q];
+        }
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        hdr[0] = (uint32_t)(carry >> 32);
+        hdr[1] = (uint32_t)carry;
+    }
+}
+
+// replicate r = r0 + blockIdx.y, draws t = 4 q .. 4 q + 3 of thread q: word t & 3 of philox4x32((t >> 2, r, BOOT_STREAM,
+// 0x5bd1e995), seed).  Plain: entry (u N) >> 32 of `table` (index order).  Stratified (hdr != null, table = strat): draws
+// t < n_pos take positive (u n_pos) >> 32, the others negative (u n_neg) >> 32.  hist[rl][bin][class] += 1, ctr[rl] += the
+// replicate's positives: integer atomics, the result does not depend on their order.
+__global__ __launch_bounds__(256) void boot_hist_k(const uint32_t* __restrict__ table, const uint32_t* __restrict__ hdr, int N,
+                                                   int r0, uint32_t seed_lo, uint32_t seed_hi, uint32_t* __restrict__ hist,
+                                                   uint32_t* __restrict__ ctr) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t np = hdr ? hdr[0] : (uint32_t)N, nn = hdr ? hdr[1] : 0u;
+    const uint4 r4 = philox4x32(q, (uint32_t)(r0 + (int)blockIdx.y), BOOT_STREAM, 0x5bd1e995u, seed_lo, seed_hi);
+    const uint32_t w[4] = {r4.x, r4.y, r4.z, r4.w};
+    uint32_t* h = hist + (size_t)blockIdx.y * (size_t)N * 2;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t t = 4u * q + k;
+        if (t >= (uint32_t)N) continue;
+        // t >= np only when stratified, and then nn = N - np >= 1: both forms stay inside the table
+        const uint32_t j = t < np ? __umulhi(w[k], np) : (uint32_t)N + __umulhi(w[k], nn);
+        const uint32_t e = table[j];
+        atomicAdd(h + 2 * (size_t)(e & 0x7fffffffu) + (e >> 31), 1u);
+        mine += e >> 31;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(ctr + blockIdx.y, mine);
+}
+
+// one workgroup per replicate: the bins in descending order, 1024 per step, cumulative (tp, fp) by a block scan with a
+// carried prefix; every sum is per thread in step order, then over the threads in a fixed tree -- the bits are a function of
+// (hist, N) alone.  The record's slots and their meaning are mc_cls_record's on the resampled multiset.
+__global__ __launch_bounds__(256) void boot_record_k(const uint32_t* __restrict__ hist, const uint32_t* __restrict__ ctr,
+                                                     const float* __restrict__ bin_score, int N, double threshold,
+                                                     u64* __restrict__ records) {
+    __shared__ u64 s_w[4];
+    __shared__ u64 s4[4];
+    __shared__ double d4[4];
+    __shared__ Best b4[4];
+    const uint32_t* h = hist + (size_t)blockIdx.x * (size_t)N * 2;
+    const u64 npos = ctr[blockIdx.x], nneg = (u64)N - npos;
+    const double dn = (double)npos;
+    u64 carry = 0;                                              // tp << 32 | fp over the bins above this step
+    u64 iv[7] = {0, 0, 0, 0, 0, 0, 0};                          // gt, eq, tp, fp, tn, fn, K
+    double f[CR_F64] = {0.0, 0.0, 0.0, 0.0};
+    Best best = {0u, 0u, -__builtin_inff()};
+    for (int base = 0; base < N; base += BOOT_TILE) {
+        const int p0 = base + 4 * (int)threadIdx.x;
+        uint32_t cp[4], cn[4];
+        u64 v = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            cp[q] = cn[q] = 0;
+            if (p0 + q < N) {
+                const uint2 c = *reinterpret_cast<const uint2*>(h + 2 * (size_t)(N - 1 - (p0 + q)));
+                cn[q] = c.x;
+                cp[q] = c.y;
+            }
+            v += ((u64)cp[q] << 32) | cn[q];
+        }
+        u64 total;
+        const u64 ex = block_excl_scan_u64(v, s_w, &total) + carry;
+        uint32_t tp0 = (uint32_t)(ex >> 32), fp0 = (uint32_t)ex;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!(cp[q] | cn[q])) continue;                     // a score absent from the replicate is no threshold of it
+            const float s = bin_score[N - 1 - (p0 + q)];
+            const uint32_t tp1 = tp0 + cp[q], fp1 = fp0 + cn[q];
+            iv[0] += (u64)cn[q] * tp0;                          // pairs won: the positives strictly above these negatives
+            iv[1] += (u64)cp[q] * cn[q];
+            const bool pred = (double)s >= threshold;
+            iv[2] += pred ? cp[q] : 0u;
+            iv[3] += pred ? cn[q] : 0u;
+            iv[4] += pred ? 0u : cn[q];
+            iv[5] += pred ? 0u : cp[q];
+            iv[6] += 1;
+            const double cs = (double)fminf(fmaxf(s, 0.f), 1.f);
+            f[2] += cs * (double)cp[q];
+            f[3] += cs * (double)cn[q];
+            if (cp[q]) {
+                const Best cand = {tp1, fp1, s};
+                if (best_better(cand, best, npos)) best = cand;
+            }
+            if (npos) {
+                const double p1 = (double)tp1 / (double)(tp1 + fp1);
+                const double pp = tp0 + fp0 ? (double)tp0 / (double)(tp0 + fp0) : 1.0;    // the curve's start: precision 1
+                const double dr = (double)tp1 / dn - (double)tp0 / dn;
+                f[0] += dr * (p1 + pp) / 2.0;
+                f[1] += dr * p1;
+            }
+            tp0 = tp1;
+            fp0 = fp1;
+        }
+        carry += total;
+    }
+    u64 tot[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) tot[q] = block_sum_u64(iv[q], s4);
+    double ftot[CR_F64];
+#pragma unroll
+    for (int q = 0; q < CR_F64; ++q) ftot[q] = block_sum_f64(f[q], d4);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const Best other = best_shfl_xor(best, o);
+        if (best_better(other, best, npos)) best = other;
+    }
+    if ((threadIdx.x & 63) == 0) b4[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < 4; ++w)
+        if (best_better(b4[w], best, npos)) best = b4[w];
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    u64* rec = records + (size_t)blockIdx.x * REC_SLOTS;
+    rec[REC_NPOS] = npos;
+    rec[REC_NNEG] = nneg;
+    rec[REC_GT] = tot[0];
+    rec[REC_EQ] = tot[1];
+    rec[REC_BEST_TP] = best.tp;
+    rec[REC_BEST_FP] = best.fp;
+    rec[REC_BEST_THR] = __float_as_uint(best.thr);
+    rec[REC_TP] = tot[2];
+    rec[REC_FP] = tot[3];
+    rec[REC_TN] = tot[4];
+    rec[REC_FN] = tot[5];
+    rec[REC_K] = tot[6];
+    rec[REC_NAN] = 0;
+    rec[REC_BADLABEL] = 0;
+    rec[REC_SPARE0] = 0;
+    rec[REC_SPARE1] = 0;
+    rec[REC_PRAUC] = (u64)__double_as_longlong(npos ? ftot[0] : nan);
+    rec[REC_AP] = (u64)__double_as_longlong(npos ? ftot[1] : nan);
+    rec[REC_CLIP_POS] = (u64)__double_as_longlong(ftot[2]);
+    rec[REC_CLIP_NEG] = (u64)__double_as_longlong(ftot[3]);
+}
+
 constexpr int CLS_MAX_N = 1 << 24;      // counts fit 32 bits, count products fit fp64 (and 64-bit integers) exactly
 
 int g_splits = 0;   // 0: chosen per call
+int g_boot_chunk = 0;   // 0: chosen per call
+int g_boot_stages = 3;
+
+// workspace of mc_boot_records: 256-byte aligned sections
+struct BootLayout { long long hdr, table, strat, bin_score, ctr, hist, bytes; int chunk; };
+BootLayout boot_layout(int N, int B) {
+    auto up = [](long long v) { return (v + 255) / 256 * 256; };
+    BootLayout l;
+    long long chunk = g_boot_chunk > 0 ? g_boot_chunk : BOOT_HIST_CAP / (8ll * N);
+    if (chunk > BOOT_MAX_CHUNK) chunk = BOOT_MAX_CHUNK;
+    if (chunk > B) chunk = B;
+    if (chunk < 1) chunk = 1;
+    l.chunk = (int)chunk;
+    l.hdr = 0;
+    l.table = 256;
+    l.strat = l.table + up(4ll * N);
+    l.bin_score = l.strat + up(8ll * N);
+    l.ctr = l.bin_score + up(4ll * N);
+    l.hist = l.ctr + up(4ll * chunk);                           // ctr and hist are adjacent: one memset clears both
+    l.bytes = l.hist + up(8ll * N * chunk);
+    return l;
+}
 
 }  // namespace
 
@@ -682,5 +912,65 @@ extern "C" int mc_cls_curve(const float* score, const unsigned int* counts, int 
     hipLaunchKernelGGL(curve_scatter_k, dim3(mc_div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, score, counts,
                        (const uint32_t*)pos_ws, N, K, tp, fp, threshold);
     MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+extern "C" int mc_boot_set_chunk(int chunk) {
+    MC_CHECK(chunk >= 0 && chunk <= BOOT_MAX_CHUNK, "boot_set_chunk: chunk outside [0, 65535]");
+    g_boot_chunk = chunk;
+    return MC_OK;
+}
+extern "C" int mc_boot_set_stages(int mask) {
+    MC_CHECK(mask >= 1 && mask <= 3, "boot_set_stages: mask outside [1, 3]");
+    g_boot_stages = mask;
+    return MC_OK;
+}
+extern "C" long long mc_boot_ws_bytes(int N, int B) {
+    if (N < 1 || N > CLS_MAX_N || B < 1 || B > BOOT_MAX_B) return 0;
+    return boot_layout(N, B).bytes;
+}
+extern "C" int mc_boot_records(const float* score, const int* label, const unsigned int* counts, int N, int B, double threshold,
+                               unsigned long long seed, int stratified, long long* records, void* ws, long long ws_bytes,
+                               void* stream) {
+    MC_CHECK(score && label && counts && records && ws, "boot_records: null pointer");
+    MC_CHECK(N >= 1 && N <= CLS_MAX_N, "boot_records: N outside [1, 2^24]");
+    MC_CHECK(B >= 1 && B <= BOOT_MAX_B, "boot_records: B outside [1, 2^20]");
+    MC_CHECK(threshold == threshold, "boot_records: the threshold is NaN");
+    const BootLayout l = boot_layout(N, B);
+    MC_CHECK(ws_bytes >= l.bytes, "boot_records: the workspace is smaller than mc_boot_ws_bytes(N, B)");
+    MC_CHECK(mc_aligned16(ws), "boot_records: the workspace is not 16-byte aligned");
+    char* base = (char*)ws;
+    uint32_t* hdr = (uint32_t*)(base + l.hdr);
+    uint32_t* table = (uint32_t*)(base + l.table);
+    uint32_t* strat = (uint32_t*)(base + l.strat);
+    float* bin_score = (float*)(base + l.bin_score);
+    uint32_t* ctr = (uint32_t*)(base + l.ctr);
+    uint32_t* hist = (uint32_t*)(base + l.hist);
+    hipStream_t st = (hipStream_t)stream;
+    if (g_boot_stages & 1) {
+        hipLaunchKernelGGL(boot_table_k, dim3(mc_div_up(N, 256)), dim3(256), 0, st, score, label, counts, N, table, bin_score);
+        MC_LAUNCH_CHECK();
+        if (stratified) {
+            hipLaunchKernelGGL(boot_strat_k, dim3(1), dim3(256), 0, st, (const uint32_t*)table, N, strat, hdr);
+            MC_LAUNCH_CHECK();
+        }
+    }
+    for (int r0 = 0; r0 < B; r0 += l.chunk) {
+        const int nr = min(l.chunk, B - r0);
+        if (g_boot_stages & 1) {
+            if (hipMemsetAsync(ctr, 0, (size_t)(l.hist - l.ctr) + (size_t)nr * N * 8, st) != hipSuccess) {
+                mc_set_error("boot_records: hipMemsetAsync failed");
+                return MC_ERR_LAUNCH;
+            }
+            hipLaunchKernelGGL(boot_hist_k, dim3(mc_div_up(mc_div_up(N, 4), 256), nr), dim3(256), 0, st,
+                               (const uint32_t*)(stratified ? strat : table), (const uint32_t*)(stratified ? hdr : nullptr), N, r0,
+                               (uint32_t)seed, (uint32_t)(seed >> 32), hist, ctr);
+            MC_LAUNCH_CHECK();
+        }
+        if (g_boot_stages & 2) {
+            hipLaunchKernelGGL(boot_record_k, dim3(nr), dim3(256), 0, st, (const uint32_t*)hist, (const uint32_t*)ctr,
+                               (const float*)bin_score, N, threshold, (u64*)records + (size_t)r0 * REC_SLOTS);
+            MC_LAUNCH_CHECK();
+        }
+    }
     return MC_OK;
 }

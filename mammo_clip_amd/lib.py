@@ -256,6 +256,10 @@ _SIGS = {
     "mc_cls_record_ws_bytes": ([I], LL),
     "mc_cls_record": ([P, P, P, I, D, P, P, P], I),
     "mc_cls_curve": ([P, P, I, I, P, P, P, P, P], I),
+    "mc_boot_ws_bytes": ([I, I], LL),
+    "mc_boot_records": ([P, P, P, I, I, D, ULL, I, P, P, LL, P], I),
+    "mc_boot_set_chunk": ([I], I),
+    "mc_boot_set_stages": ([I], I),
     "mc_augment_ws_bytes": ([I, I, I], LL),
     "mc_augment_u8": ([P, LL, LL, LL, I, P, I, P, I, I, I, P, P, LL, P], I),
     "mc_augment_set_stages": ([I], I),

@@ -1752,6 +1752,36 @@ def cls_curve(score, counts, k):
     return tp, fp, thr
 
 
+BOOT_MAX_REPLICATES = 1 << 20
+
+
+def boot_records(score, label, counts, n_boot, threshold=0.5, seed=0, stratified=False):
+    """int64 [n_boot, 20] on the device: one cls_record per bootstrap replicate of the N samples (the draw and the record are
+    specified in breastclip/evaluator.py and DESIGN.md section 9q).  ``counts``: what rank_counts returned for these scores
+    and labels.  Bit-reproducible; the replicate indices depend on (seed, N, the class counts when stratified) only."""
+    label = _score_label("boot_records", score, label)
+    _rank_counts_arg("boot_records", score, counts)
+    n, b = score.numel(), int(n_boot)
+    if not 1 <= b <= BOOT_MAX_REPLICATES:
+        raise L.MammoClipHipError(f"boot_records: n_boot outside [1, {BOOT_MAX_REPLICATES}]")
+    nbytes = L.load().mc_boot_ws_bytes(n, b)
+    records = empty((b, 20), torch.int64, score)
+    ws = empty((max(1, nbytes),), torch.uint8, score)
+    L.call("mc_boot_records", _p(score), _p(label), _p(counts), n, b, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF,
+           int(bool(stratified)), _p(records), _p(ws), nbytes, _st())
+    return records
+
+
+def boot_set_chunk(chunk):
+    """replicates per chunk of boot_records (0: chosen per call); the records do not depend on it"""
+    L.call("mc_boot_set_chunk", int(chunk))
+
+
+def boot_set_stages(mask):
+    """bit 0: tables and histograms, bit 1: the record scan; 3 is the op (timing switch of scripts/boot_metrics_bench.py)"""
+    L.call("mc_boot_set_stages", int(mask))
+
+
 # ------------------------------------------------------------------------------------------- training augmentation
 def augment_u8(src, params, sigma, out=None, ws_bytes=None):
     """uint8 [n, 3, H, W]: flips / affine / elastic warp of the planes ``src`` (uint8 [n_src, H, W], any strides) under the
