@@ -2,29 +2,28 @@
 // torch.optim.AdamW over ALL parameters; trainer_ddp.py:300-303 steps it once per iteration].
 // HBM-bound: 16 B read + 12 B written per element (param, grad, exp_avg, exp_avg_sq), ~3.9 GB for the 138 M-parameter
 // B5 + BERT model; a parameter that is consumed as a bf16 matrix gets its bf16 image rewritten by the same pass (+2 B)
-// instead of by a cast kernel of its own in the next forward.  Up to PACK tensors go into one launch (pointers travel as kernel arguments, no device
-// table to keep in sync); a workgroup owns one CHUNK of one tensor, found by a scan over the pack's chunk prefix.
+// instead of by a cast kernel of its own in the next forward.  The packing of a tensor list into launches, the lookup of a
+// workgroup's chunk and the pieces shared with the SGD step are multi_tensor.h's.
 // mc_adamw_step_ema folds an exponential moving average of the weights into the same pass: the shadow of every updated
 // element is read and written while the parameter is still in registers (+8 B per element, no second read of the parameter);
 // mc_ema_update is the stand-alone form for tensors the optimizer pass does not cover (12 B per element).
+// The file also holds the gradient passes of the loss-scaled and the clipped step (unscale, non-finite flag, norm) and the
+// loss-scale update.  Kernels and host helpers first, the extern "C" entry points together at the end.
 #include <cfloat>
 #include <type_traits>
-#include "common_hip.h"
+#include "multi_tensor.h"
 #include "../../include/mammoclip_hip.h"
 
 namespace {
 
-constexpr int PACK = 40;             // tensors per launch: 40 * 44 B + scalars stays far below the 4 KB argument limit
-constexpr int CHUNK = 16384;         // elements per workgroup: 64 KB per stream in flight across its 256 lanes
-
+// ---- AdamW
 struct AdamPack {
     bf16_t* img[PACK];               // optional bf16 image of the updated parameter (nullptr: none)
     float* p[PACK];
     const float* g[PACK];
     float* m[PACK];
     float* v[PACK];
-    int first_chunk[PACK + 1];       // prefix of chunk counts
-    long long n[PACK];
+    PackIndex ix;
 };
 
 struct AdamScalars {
@@ -36,17 +35,18 @@ struct AdamScalars {
     float eps;
 };
 
-// FORM: how the sum of two products in the second moment is contracted.  0 leaves it to the compiler, which under
-// -ffp-contract=fast takes fma(beta2, v, (c g) g) in some bodies of the kernel and fma(c g, g, beta2 v) in others (1 and 2:
-// each written out) -- two roundings that differ in the last bit.  Every other expression has one product per sum.
-template <int FORM = 0>
+// FORM: which of the two products of the second moment, beta2 v + ((1 - beta2) g) g, is rounded before the fused multiply-add
+// takes the other.  1: fma(beta2, v, ((1 - beta2) g) g); 2: fma((1 - beta2) g, g, beta2 v).  The two differ in the last bit, so
+// the form is part of the kernel's arithmetic and is written out; the kernel says which body uses which.  Every other
+// expression has one product per sum, which -ffp-contract=fast fuses in one way only.
+template <int FORM>
 __device__ __forceinline__ void adamw1(float& p, float g, float& m, float& v, const AdamScalars& s) {
+    static_assert(FORM == 1 || FORM == 2, "the second-moment form is always stated");
     // same operation order as torch's AdamW: decoupled decay first, moments, then the bias-corrected step
     p -= s.lr_wd * p;
     m = m + s.one_m_beta1 * (g - m);
     if (FORM == 1) v = __builtin_fmaf(s.beta2, v, (s.one_m_beta2 * g) * g);
-    else if (FORM == 2) v = __builtin_fmaf(s.one_m_beta2 * g, g, s.beta2 * v);
-    else v = s.beta2 * v + s.one_m_beta2 * g * g;
+    else v = __builtin_fmaf(s.one_m_beta2 * g, g, s.beta2 * v);
     const float denom = sqrtf(v) * s.inv_bc2_sqrt + s.eps;
     p -= s.step_size * (m / denom);
 }
@@ -62,50 +62,18 @@ struct AdamLs {
     const float* grad_coef;    // CLIP only: the clip coefficient of mc_grad_norm, a device scalar
 };
 
-// g * c rounded once to fp32, the value torch.Tensor.mul_ would have stored.  Written as the instruction: under
-// -ffp-contract=fast a C++ product would be fused into the (g - m) and g * g that consume it, which is another rounding.
-__device__ __forceinline__ float mul_rn(float g, float c) {
-    asm("v_mul_f32 %0, %1, %0" : "+v"(g) : "s"(c));     // c is uniform: a scalar operand, the product replaces g in place
-    return g;
-}
-__device__ __forceinline__ void mul_rn4(float4& g, float c) {
-    g.x = mul_rn(g.x, c); g.y = mul_rn(g.y, c); g.z = mul_rn(g.z, c); g.w = mul_rn(g.w, c);
-}
-
-// Weight EMA: e <- e + w * (p - e) as three separately rounded fp32 operations (sub, mul, add: what three tensor operations of
-// torch give on any IEEE host).  The product is the instruction, like the clip product above: under -ffp-contract=fast a C++
-// product would be fused into the sum that consumes it.  w = (float)(1 - d_k), d_k = min(decay, (1 + k) / (10 + k)) with
-// warm-up, decay without, in double; k = *count + 1: the applied updates so far, a device integer, plus this one.  Every
-// launch of one update reads the same count; mc_ema_tick advances it afterwards.
 struct NoEma {};
-struct AdamEma {
+struct AdamEma {                     // the weight EMA of multi_tensor.h, for the tensors of the pack
     float* e[PACK];                  // shadow of pk.p[t]
     const long long* count;
     double decay;
     int warmup;
 };
 
-__device__ __forceinline__ float ema_weight(const long long* __restrict__ count, double decay, int warmup) {
-    double d = decay;
-    if (warmup) {
-        const double k = (double)(*count + 1);
-        const double r = (1.0 + k) / (10.0 + k);
-        if (r < d) d = r;
-    }
-    return (float)(1.0 - d);
-}
-__device__ __forceinline__ void ema1(float& e, float p, float w) {
-    float s = p - e;
-    asm("v_mul_f32 %0, %1, %0" : "+v"(s) : "v"(w));      // (w comes out of fp64 arithmetic: a vector register)
-    e = e + s;
-}
-__device__ __forceinline__ void ema4(float4& e, const float4& p, float w) {
-    ema1(e.x, p.x, w); ema1(e.y, p.y, w); ema1(e.z, p.z, w); ema1(e.w, p.w, w);
-}
-
 // CLIP: every gradient is multiplied by *ls.grad_coef as it is loaded (gradient-norm clipping without rewriting the
-// gradients in memory); CLIP = false is the kernel as it was.  EMA: the shadow em.e[t] of every updated element follows in the
-// same pass (a skipped step returns before it, like before everything else); EMA = false is the kernel as it was.
+// gradients in memory; mul_rn_u: under -ffp-contract=fast a C++ product would be fused into the (g - m) and g * g that consume
+// it, which is another rounding); CLIP = false is the kernel as it was.  EMA: the shadow em.e[t] of every updated element
+// follows in the same pass (a skipped step returns before it, like before everything else); EMA = false is the kernel as it was.
 template <bool CLIP, bool EMA>
 __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, AdamScalars s, AdamLs ls,
                                                      std::conditional_t<EMA, AdamEma, NoEma> em) {
@@ -123,29 +91,23 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
         s.inv_bc2_sqrt = s_dev[1];
     }
     const float c = CLIP ? *ls.grad_coef : 1.f;
-    // The instantiations without EMA are compiled as they always were (FORM 0).  Those with EMA have to give their results
-    // bit for bit, and the extra loads move the compiler's choice, so each body is pinned to what its counterpart compiles to:
-    // the vector bodies of the plain kernel to form 2, its ragged tail and scalar body and all of the clip kernel to form 1
-    // (read off the generated code of both; tests/test_ema_gpu.py compares the bits on every path).
-    constexpr int FV = !EMA ? 0 : CLIP ? 1 : 2, FS = !EMA ? 0 : 1;
+    // Second-moment form (adamw1) of each body, with and without EMA: the float4 bodies of the kernel without clip use form 2;
+    // its ragged tail and scalar body, and every body of the clip kernel, use form 1.  tests/test_adamw_bits_gpu.py holds the
+    // bits of every body to recorded ones, tests/test_ema_gpu.py those of the EMA instantiations to the plain ones.
+    constexpr int FV = CLIP ? 1 : 2, FS = 1;
     float w = 0.f;
     if constexpr (EMA) w = ema_weight(em.count, em.decay, em.warmup);
-    int t = 0;
-    const int blk = blockIdx.x;
-    while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;       // uniform scan, <= PACK scalar compares
-    const long long n = pk.n[t];
-    const long long base = (long long)(blk - pk.first_chunk[t]) * CHUNK;
-    float* __restrict__ p = pk.p[t] + base;
-    const float* __restrict__ g = pk.g[t] + base;
-    float* __restrict__ m = pk.m[t] + base;
-    float* __restrict__ v = pk.v[t] + base;
-    bf16_t* __restrict__ img = pk.img[t] ? pk.img[t] + base : nullptr;      // base is a multiple of 16384: alignment kept
-    const long long left = n - base;
-    const int len = left < CHUNK ? (int)left : CHUNK;
+    const ChunkRef ck = chunk_of_block(pk.ix, count);
+    const long long t = ck.t;
+    float* __restrict__ p = pk.p[t] + ck.base;
+    const float* __restrict__ g = pk.g[t] + ck.base;
+    float* __restrict__ m = pk.m[t] + ck.base;
+    float* __restrict__ v = pk.v[t] + ck.base;
+    bf16_t* __restrict__ img = pk.img[t] ? pk.img[t] + ck.base : nullptr;
+    const int len = ck.len();
     float* __restrict__ e = nullptr;
-    if constexpr (EMA) e = em.e[t] + base;
-    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)e)) & 15) == 0 &&
-                     (((uintptr_t)img) & 7) == 0;
+    if constexpr (EMA) e = em.e[t] + ck.base;
+    const bool vec = (addr_bits(p, g, m, v, e) & 15) == 0 && (addr_bits(img) & 7) == 0;
     int i = threadIdx.x * 4;
     if (vec) {
         // 2 float4 per array in flight per lane (8 loads) before the first use
@@ -156,7 +118,7 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
             float4 V0 = *(const float4*)(v + i), V1 = *(const float4*)(v + i + 1024);
             float4 E0, E1;
             if constexpr (EMA) { E0 = *(const float4*)(e + i); E1 = *(const float4*)(e + i + 1024); }
-            if (CLIP) { mul_rn4(G0, c); mul_rn4(G1, c); }
+            if (CLIP) { mul_rn4_u(G0, c); mul_rn4_u(G1, c); }
             adamw1<FV>(P0.x, G0.x, M0.x, V0.x, s); adamw1<FV>(P0.y, G0.y, M0.y, V0.y, s);
             adamw1<FV>(P0.z, G0.z, M0.z, V0.z, s); adamw1<FV>(P0.w, G0.w, M0.w, V0.w, s);
             adamw1<FV>(P1.x, G1.x, M1.x, V1.x, s); adamw1<FV>(P1.y, G1.y, M1.y, V1.y, s);
@@ -168,42 +130,81 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
                 ema4(E0, P0, w); ema4(E1, P1, w);
                 *(float4*)(e + i) = E0; *(float4*)(e + i + 1024) = E1;
             }
-            if (img) {
-                *(uint2*)(img + i) = make_uint2(pack_bf2(P0.x, P0.y), pack_bf2(P0.z, P0.w));
-                *(uint2*)(img + i + 1024) = make_uint2(pack_bf2(P1.x, P1.y), pack_bf2(P1.z, P1.w));
-            }
+            if (img) { store_image4(img + i, P0); store_image4(img + i + 1024, P1); }
         }
         for (; i + 3 < len; i += 1024) {
             float4 P0 = *(const float4*)(p + i), G0 = *(const float4*)(g + i);
             float4 M0 = *(const float4*)(m + i), V0 = *(const float4*)(v + i);
             float4 E0;
             if constexpr (EMA) E0 = *(const float4*)(e + i);
-            if (CLIP) mul_rn4(G0, c);
+            if (CLIP) mul_rn4_u(G0, c);
             adamw1<FV>(P0.x, G0.x, M0.x, V0.x, s); adamw1<FV>(P0.y, G0.y, M0.y, V0.y, s);
             adamw1<FV>(P0.z, G0.z, M0.z, V0.z, s); adamw1<FV>(P0.w, G0.w, M0.w, V0.w, s);
             *(float4*)(p + i) = P0; *(float4*)(m + i) = M0; *(float4*)(v + i) = V0;
             if constexpr (EMA) { ema4(E0, P0, w); *(float4*)(e + i) = E0; }
-            if (img) *(uint2*)(img + i) = make_uint2(pack_bf2(P0.x, P0.y), pack_bf2(P0.z, P0.w));
+            if (img) store_image4(img + i, P0);
         }
         // ragged tail of the chunk: the (< 4) elements after the last whole float4
         const int done = len & ~3;
         const int j = done + threadIdx.x;
         if (j < len) {
             float P = p[j], M = m[j], V = v[j];
-            adamw1<FS>(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
+            adamw1<FS>(P, CLIP ? mul_rn_u(g[j], c) : g[j], M, V, s);
             p[j] = P; m[j] = M; v[j] = V;
             if constexpr (EMA) { float E = e[j]; ema1(E, P, w); e[j] = E; }
-            if (img) img[j] = f2bf(P);
+            if (img) store_image1(img + j, P);
         }
     } else {
         for (int j = threadIdx.x; j < len; j += 256) {
             float P = p[j], M = m[j], V = v[j];
-            adamw1<FS>(P, CLIP ? mul_rn(g[j], c) : g[j], M, V, s);
+            adamw1<FS>(P, CLIP ? mul_rn_u(g[j], c) : g[j], M, V, s);
             p[j] = P; m[j] = M; v[j] = V;
             if constexpr (EMA) { float E = e[j]; ema1(E, P, w); e[j] = E; }
-            if (img) img[j] = f2bf(P);
+            if (img) store_image1(img + j, P);
         }
     }
+}
+
+// shadows == nullptr: no EMA (decay, warmup and count are not looked at).  The entry points have checked what is theirs alone.
+int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
+               long long step, const float* grad_coef, const float* found_inf, const float* skipped, float* const* shadows,
+               double decay, int warmup, const long long* count, void* stream) {
+    MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0), "adamw: bad tensor list");
+    MC_CHECK(step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adamw: bad hyper-parameters");
+    for (int i = 0; i < n_tensors; ++i) {                       // every argument is checked before the first launch
+        const mc_adamw_tensor& t = tensors[i];
+        MC_CHECK(t.numel == 0 || (t.param && t.grad && t.exp_avg && t.exp_avg_sq && t.numel > 0), "adamw: null tensor pointer");
+    }
+    // scalars are derived in double like torch does on the host (1 - 0.999 in fp32 is already 1.3e-5 off)
+    AdamScalars s;
+    s.lr_wd = (float)(lr * weight_decay);
+    s.beta1 = (float)beta1; s.beta2 = (float)beta2;
+    s.one_m_beta1 = (float)(1.0 - beta1); s.one_m_beta2 = (float)(1.0 - beta2);
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    s.step_size = (float)(lr / bc1);
+    s.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    s.eps = (float)eps;
+    AdamLs ls;
+    ls.found_inf = found_inf; ls.skipped = skipped; ls.lr = lr; ls.beta1 = beta1; ls.beta2 = beta2; ls.step = step;
+    ls.grad_coef = grad_coef;
+    AdamEma em;
+    em.count = count; em.decay = decay; em.warmup = warmup;
+    return multi_tensor_launch<AdamPack>(
+        n_tensors, "adamw: tensor too large", [&](int i) { return tensors[i].numel; },
+        [&](AdamPack& pk, int slot, int i) {
+            const mc_adamw_tensor& t = tensors[i];
+            pk.p[slot] = t.param; pk.g[slot] = t.grad; pk.m[slot] = t.exp_avg; pk.v[slot] = t.exp_avg_sq;
+            pk.img[slot] = t.bf16_image;
+            if (shadows) em.e[slot] = shadows[i];
+        },
+        [&](const AdamPack& pk, int cnt, int chunks, long long) {
+            if (shadows)
+                hipLaunchKernelGGL((grad_coef ? adamw_multi_k<true, true> : adamw_multi_k<false, true>), dim3(chunks), dim3(256), 0,
+                                   (hipStream_t)stream, pk, cnt, s, ls, em);
+            else
+                hipLaunchKernelGGL((grad_coef ? adamw_multi_k<true, false> : adamw_multi_k<false, false>), dim3(chunks), dim3(256), 0,
+                                   (hipStream_t)stream, pk, cnt, s, ls, NoEma{});
+        });
 }
 
 // ---- stand-alone weight EMA: shadow <- shadow + w * (source - shadow) for a list of tensors (buffers, parameters the optimizer
@@ -212,24 +213,19 @@ __global__ void __launch_bounds__(256) adamw_multi_k(AdamPack pk, int count, Ada
 struct EmaPack {
     float* e[PACK];
     const float* p[PACK];
-    int first_chunk[PACK + 1];
-    long long n[PACK];
+    PackIndex ix;
 };
 
 __global__ void __launch_bounds__(256) ema_multi_k(EmaPack pk, int count, const long long* __restrict__ applied, double decay,
                                                    int warmup, const float* __restrict__ found_inf) {
     if (found_inf && *found_inf != 0.f) return;                        // (uniform: the whole grid leaves)
     const float w = ema_weight(applied, decay, warmup);
-    int t = 0;
-    const int blk = blockIdx.x;
-    while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;
-    const long long base = (long long)(blk - pk.first_chunk[t]) * CHUNK;
-    float* __restrict__ e = pk.e[t] + base;
-    const float* __restrict__ p = pk.p[t] + base;
-    const long long left = pk.n[t] - base;
-    const int len = left < CHUNK ? (int)left : CHUNK;
+    const ChunkRef ck = chunk_of_block(pk.ix, count);
+    float* __restrict__ e = pk.e[ck.t] + ck.base;
+    const float* __restrict__ p = pk.p[ck.t] + ck.base;
+    const int len = ck.len();
     int i = threadIdx.x * 4;
-    if (((((uintptr_t)e) | ((uintptr_t)p)) & 15) == 0) {
+    if ((addr_bits(e, p) & 15) == 0) {
         // 4 float4 per array in flight per lane (8 loads) before the first use, like the optimizer pass
         for (; i + 3 * 1024 + 3 < len; i += 4096) {
             float4 E[4], P[4];
@@ -258,13 +254,14 @@ __global__ void ema_tick_k(long long* __restrict__ applied, const float* __restr
     *applied += 1;
 }
 
+inline bool ema_decay_ok(double decay) { return decay > 0.0 && decay < 1.0; }            // (false for nan)
+
 // ---- gradient unscale + non-finite check of the loss-scaled (f16 storage) step [ref: trainer.py:271-278 runs the backward
 // under torch.cuda.amp.GradScaler: scaler.step() = unscale the gradients, skip the update if any is inf / nan].
 // Same packing as the update kernel: a workgroup owns one CHUNK of one gradient tensor.
 struct UnscalePack {
     float* g[PACK];
-    int first_chunk[PACK + 1];
-    long long n[PACK];
+    PackIndex ix;
 };
 
 // torch.isfinite's answer: +-FLT_MAX is a finite gradient, inf and nan (every compare with nan is false) are not
@@ -285,7 +282,7 @@ template <bool STORE, bool NORM>
 __device__ __forceinline__ double chunk_pass(float* __restrict__ g, int len, float mul, bool& bad) {
     double acc = 0.0;
     int i = threadIdx.x * 4;
-    if ((((uintptr_t)g) & 15) == 0) {
+    if ((addr_bits(g) & 15) == 0) {
         // 4 float4 in flight per lane before the first use (one load at a time leaves the pass latency-bound at less than
         // half of the HBM rate); the values are consumed in index order either way, so the lane's sum does not change
         for (; i + 3 * 1024 + 3 < len; i += 4096) {
@@ -335,20 +332,15 @@ __global__ void __launch_bounds__(256) grads_pass_k(UnscalePack pk, int count, f
         if (scale_dev) mul = 1.0f / *scale_dev;                         // the dynamic scale lives on the device (no host sync)
         else if (mul_dev) mul = *mul_dev;
     }
-    int t = 0;
-    const int blk = blockIdx.x;
-    while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;
-    const long long base = (long long)(blk - pk.first_chunk[t]) * CHUNK;
-    float* __restrict__ g = pk.g[t] + base;
-    const long long left = pk.n[t] - base;
-    const int len = left < CHUNK ? (int)left : CHUNK;
+    const ChunkRef ck = chunk_of_block(pk.ix, count);
+    float* __restrict__ g = pk.g[ck.t] + ck.base;
     bool bad = false;
-    const double acc = chunk_pass<STORE, NORM>(g, len, mul, bad);
+    const double acc = chunk_pass<STORE, NORM>(g, ck.len(), mul, bad);
     if (STORE && bad && found_inf) *found_inf = 1.0f;          // (every writer stores the same value)
     if (NORM) {
         __shared__ double sh[256];
         const double tot = block_sum256(acc, sh);
-        if (threadIdx.x == 0) partials[blk] = tot;
+        if (threadIdx.x == 0) partials[blockIdx.x] = tot;
     }
 }
 
@@ -365,7 +357,7 @@ __global__ void __launch_bounds__(256) grad_norm_finish_k(const double* __restri
     const double tot = block_sum256(acc, sh);
     if (threadIdx.x == 0) {
         const float nrm = (float)sqrt(tot);
-        const float c = mul_rn((float)(1.0 / (double)(nrm + 1e-6f)), max_norm);
+        const float c = mul_rn_u((float)(1.0 / (double)(nrm + 1e-6f)), max_norm);
         out[0] = nrm;
         out[1] = c > 1.0f ? 1.0f : c;
     }
@@ -395,20 +387,6 @@ __global__ void loss_scale_update_k(float* __restrict__ st, float* __restrict__ 
     st[2] = 0.f;
 }
 
-enum GradPass { GP_UNSCALE, GP_UNSCALE_NORM, GP_NORM };
-int grads_pass_impl(GradPass mode, const mc_adamw_tensor* tensors, int n_tensors, float mul, const float* scale_dev,
-                    const float* mul_dev, float* found_inf, double* partials, void* stream);
-int grad_norm_finish(const double* partials, long long n, float max_norm, float* out2, void* stream);
-struct EmaHost {                       // the EMA arguments of a call (nullptr: none)
-    float* const* shadows;             // parallel to the tensor list
-    double decay;
-    int warmup;
-    const long long* count;
-};
-int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
-               long long step, const float* grad_coef, const float* found_inf, const float* skipped, const EmaHost* ema, void* stream);
-inline bool ema_decay_ok(double decay) { return decay > 0.0 && decay < 1.0; }            // (false for nan)
-
 // chunks (= doubles of norm workspace) of a gradient list, -1 on a bad one; need_grad: every non-empty tensor has a pointer
 long long list_chunks(const mc_adamw_tensor* tensors, int n_tensors, bool need_grad) {
     if (n_tensors < 0 || (!tensors && n_tensors > 0)) return -1;
@@ -420,7 +398,92 @@ long long list_chunks(const mc_adamw_tensor* tensors, int n_tensors, bool need_g
     return tot;
 }
 
+enum GradPass { GP_UNSCALE, GP_UNSCALE_NORM, GP_NORM };
+int grads_pass_impl(GradPass mode, const mc_adamw_tensor* tensors, int n_tensors, float mul, const float* scale_dev,
+                    const float* mul_dev, float* found_inf, double* partials, void* stream) {
+    for (int i = 0; i < n_tensors; ++i)                         // every argument is checked before the first launch
+        MC_CHECK(tensors[i].numel == 0 || (tensors[i].grad && tensors[i].numel > 0), "grads_unscale: null gradient pointer");
+    auto k = mode == GP_UNSCALE ? grads_pass_k<true, false> : mode == GP_UNSCALE_NORM ? grads_pass_k<true, true> : grads_pass_k<false, true>;
+    return multi_tensor_launch<UnscalePack>(
+        n_tensors, "grads_unscale: tensor too large", [&](int i) { return tensors[i].numel; },
+        [&](UnscalePack& pk, int slot, int i) { pk.g[slot] = const_cast<float*>(tensors[i].grad); },
+        [&](const UnscalePack& pk, int cnt, int chunks, long long chunk_base) {
+            hipLaunchKernelGGL(k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, mul, scale_dev, mul_dev, found_inf,
+                               partials ? partials + chunk_base : nullptr);
+        });
+}
+
+int grad_norm_finish(const double* partials, long long n, float max_norm, float* out2, void* stream) {
+    hipLaunchKernelGGL(grad_norm_finish_k, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out2);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
+
 }  // namespace
+
+// ---- entry points (include/mammoclip_hip.h)
+extern "C" int mc_adamw_step(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
+                             double eps, double weight_decay, long long step, void* stream) {
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, nullptr, nullptr, 0.0, 0, nullptr,
+                      stream);
+}
+
+extern "C" int mc_adamw_step_ls(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
+                                double eps, double weight_decay, long long step, const float* found_inf, const float* skipped,
+                                void* stream) {
+    MC_CHECK(found_inf && skipped, "adamw_step_ls: null loss-scale state");
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, found_inf, skipped, nullptr, 0.0, 0, nullptr,
+                      stream);
+}
+
+extern "C" int mc_adamw_step_clip(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
+                                  double eps, double weight_decay, long long step, const float* grad_coef, const float* found_inf,
+                                  const float* skipped, void* stream) {
+    MC_CHECK(grad_coef, "adamw_step_clip: null grad_coef");
+    MC_CHECK((found_inf == nullptr) == (skipped == nullptr), "adamw_step_clip: found_inf and skipped are both null or both set");
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, nullptr, 0.0, 0, nullptr,
+                      stream);
+}
+
+extern "C" int mc_adamw_step_ema(const mc_adamw_tensor* tensors, float* const* shadows, int n_tensors, double lr, double beta1,
+                                 double beta2, double eps, double weight_decay, long long step, double decay, int warmup,
+                                 const long long* count, const float* grad_coef, const float* found_inf, const float* skipped,
+                                 void* stream) {
+    MC_CHECK(n_tensors >= 0 && ((tensors && shadows) || n_tensors == 0), "adamw_step_ema: bad tensor or shadow list");
+    MC_CHECK(ema_decay_ok(decay), "adamw_step_ema: decay must lie strictly between 0 and 1");
+    MC_CHECK(count, "adamw_step_ema: null update count");
+    MC_CHECK((found_inf == nullptr) == (skipped == nullptr), "adamw_step_ema: found_inf and skipped are both null or both set");
+    for (int i = 0; i < n_tensors; ++i) {
+        MC_CHECK(tensors[i].numel >= 0, "adamw_step_ema: negative size");
+        MC_CHECK(tensors[i].numel == 0 || shadows[i], "adamw_step_ema: null shadow pointer");
+    }
+    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, shadows, decay,
+                      warmup != 0, count, stream);
+}
+
+extern "C" int mc_ema_update(float* const* shadows, const float* const* sources, const long long* numel, int n_tensors, double decay,
+                             int warmup, const long long* count, const float* found_inf, void* stream) {
+    MC_CHECK(n_tensors >= 0 && ((shadows && sources && numel) || n_tensors == 0), "ema_update: bad tensor lists");
+    MC_CHECK(ema_decay_ok(decay), "ema_update: decay must lie strictly between 0 and 1");
+    MC_CHECK(count, "ema_update: null update count");
+    for (int i = 0; i < n_tensors; ++i) {                       // every argument is checked before the first launch
+        MC_CHECK(numel[i] >= 0, "ema_update: negative size");
+        MC_CHECK(numel[i] == 0 || (shadows[i] && sources[i]), "ema_update: null tensor pointer");
+    }
+    return multi_tensor_launch<EmaPack>(
+        n_tensors, "ema_update: tensor too large", [&](int i) { return numel[i]; },
+        [&](EmaPack& pk, int slot, int i) { pk.e[slot] = shadows[i]; pk.p[slot] = sources[i]; },
+        [&](const EmaPack& pk, int cnt, int chunks, long long) {
+            hipLaunchKernelGGL(ema_multi_k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, count, decay, warmup != 0, found_inf);
+        });
+}
+
+extern "C" int mc_ema_tick(long long* count, const float* found_inf, void* stream) {
+    MC_CHECK(count, "ema_tick: null update count");
+    hipLaunchKernelGGL(ema_tick_k, dim3(1), dim3(64), 0, (hipStream_t)stream, count, found_inf);
+    MC_LAUNCH_CHECK();
+    return MC_OK;
+}
 
 extern "C" int mc_grads_unscale(const mc_adamw_tensor* tensors, int n_tensors, float inv_scale, float* found_inf, void* stream) {
     MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0) && found_inf, "grads_unscale: bad arguments");
@@ -477,176 +540,3 @@ extern "C" int mc_loss_scale_update(float* state, float* opt_skipped, double gro
     MC_LAUNCH_CHECK();
     return MC_OK;
 }
-
-namespace {
-int grads_pass_impl(GradPass mode, const mc_adamw_tensor* tensors, int n_tensors, float mul, const float* scale_dev,
-                    const float* mul_dev, float* found_inf, double* partials, void* stream) {
-    UnscalePack pk;
-    int cnt = 0, chunks = 0;
-    long long chunk_base = 0;                // chunks of the launches before this one: where its partials start
-    auto flush = [&]() -> int {
-        if (cnt == 0) return MC_OK;
-        pk.first_chunk[cnt] = chunks;
-        double* part = partials ? partials + chunk_base : nullptr;
-        auto k = mode == GP_UNSCALE ? grads_pass_k<true, false> : mode == GP_UNSCALE_NORM ? grads_pass_k<true, true> : grads_pass_k<false, true>;
-        hipLaunchKernelGGL(k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, mul, scale_dev, mul_dev, found_inf, part);
-        MC_LAUNCH_CHECK();
-        chunk_base += chunks;
-        cnt = 0; chunks = 0;
-        return MC_OK;
-    };
-    for (int i = 0; i < n_tensors; ++i) {
-        const mc_adamw_tensor& t = tensors[i];
-        if (t.numel == 0) continue;
-        MC_CHECK(t.grad && t.numel > 0, "grads_unscale: null gradient pointer");
-        const long long nch = (t.numel + CHUNK - 1) / CHUNK;
-        MC_CHECK(nch < (1ll << 30), "grads_unscale: tensor too large");
-        if (cnt == PACK || (long long)chunks + nch > (1ll << 30)) {
-            int r = flush();
-            if (r != MC_OK) return r;
-        }
-        pk.g[cnt] = const_cast<float*>(t.grad); pk.n[cnt] = t.numel; pk.first_chunk[cnt] = chunks;
-        chunks += (int)nch;
-        ++cnt;
-    }
-    return flush();
-}
-
-int grad_norm_finish(const double* partials, long long n, float max_norm, float* out2, void* stream) {
-    hipLaunchKernelGGL(grad_norm_finish_k, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm, out2);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-}  // namespace
-
-extern "C" int mc_adamw_step(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
-                             double eps, double weight_decay, long long step, void* stream) {
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int mc_adamw_step_ls(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
-                                double eps, double weight_decay, long long step, const float* found_inf, const float* skipped,
-                                void* stream) {
-    MC_CHECK(found_inf && skipped, "adamw_step_ls: null loss-scale state");
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, nullptr, found_inf, skipped, nullptr, stream);
-}
-
-extern "C" int mc_adamw_step_clip(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
-                                  double eps, double weight_decay, long long step, const float* grad_coef, const float* found_inf,
-                                  const float* skipped, void* stream) {
-    MC_CHECK(grad_coef, "adamw_step_clip: null grad_coef");
-    MC_CHECK((found_inf == nullptr) == (skipped == nullptr), "adamw_step_clip: found_inf and skipped are both null or both set");
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, nullptr, stream);
-}
-
-extern "C" int mc_adamw_step_ema(const mc_adamw_tensor* tensors, float* const* shadows, int n_tensors, double lr, double beta1,
-                                 double beta2, double eps, double weight_decay, long long step, double decay, int warmup,
-                                 const long long* count, const float* grad_coef, const float* found_inf, const float* skipped,
-                                 void* stream) {
-    MC_CHECK(n_tensors >= 0 && ((tensors && shadows) || n_tensors == 0), "adamw_step_ema: bad tensor or shadow list");
-    MC_CHECK(ema_decay_ok(decay), "adamw_step_ema: decay must lie strictly between 0 and 1");
-    MC_CHECK(count, "adamw_step_ema: null update count");
-    MC_CHECK((found_inf == nullptr) == (skipped == nullptr), "adamw_step_ema: found_inf and skipped are both null or both set");
-    for (int i = 0; i < n_tensors; ++i) {
-        MC_CHECK(tensors[i].numel >= 0, "adamw_step_ema: negative size");
-        MC_CHECK(tensors[i].numel == 0 || shadows[i], "adamw_step_ema: null shadow pointer");
-    }
-    const EmaHost ema{shadows, decay, warmup != 0, count};
-    return adamw_impl(tensors, n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_coef, found_inf, skipped, &ema, stream);
-}
-
-extern "C" int mc_ema_update(float* const* shadows, const float* const* sources, const long long* numel, int n_tensors, double decay,
-                             int warmup, const long long* count, const float* found_inf, void* stream) {
-    MC_CHECK(n_tensors >= 0 && ((shadows && sources && numel) || n_tensors == 0), "ema_update: bad tensor lists");
-    MC_CHECK(ema_decay_ok(decay), "ema_update: decay must lie strictly between 0 and 1");
-    MC_CHECK(count, "ema_update: null update count");
-    for (int i = 0; i < n_tensors; ++i) {                       // every argument is checked before the first launch
-        MC_CHECK(numel[i] >= 0, "ema_update: negative size");
-        MC_CHECK(numel[i] == 0 || (shadows[i] && sources[i]), "ema_update: null tensor pointer");
-        MC_CHECK((numel[i] + CHUNK - 1) / CHUNK < (1ll << 30), "ema_update: tensor too large");
-    }
-    EmaPack pk;
-    int cnt = 0, chunks = 0;
-    auto flush = [&]() -> int {
-        if (cnt == 0) return MC_OK;
-        pk.first_chunk[cnt] = chunks;
-        hipLaunchKernelGGL(ema_multi_k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, count, decay, warmup != 0, found_inf);
-        MC_LAUNCH_CHECK();
-        cnt = 0; chunks = 0;
-        return MC_OK;
-    };
-    for (int i = 0; i < n_tensors; ++i) {
-        if (numel[i] == 0) continue;
-        const long long nch = (numel[i] + CHUNK - 1) / CHUNK;
-        if (cnt == PACK || (long long)chunks + nch > (1ll << 30)) {
-            int r = flush();
-            if (r != MC_OK) return r;
-        }
-        pk.e[cnt] = shadows[i]; pk.p[cnt] = sources[i]; pk.n[cnt] = numel[i]; pk.first_chunk[cnt] = chunks;
-        chunks += (int)nch;
-        ++cnt;
-    }
-    return flush();
-}
-
-extern "C" int mc_ema_tick(long long* count, const float* found_inf, void* stream) {
-    MC_CHECK(count, "ema_tick: null update count");
-    hipLaunchKernelGGL(ema_tick_k, dim3(1), dim3(64), 0, (hipStream_t)stream, count, found_inf);
-    MC_LAUNCH_CHECK();
-    return MC_OK;
-}
-
-namespace {
-int adamw_impl(const mc_adamw_tensor* tensors, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
-               long long step, const float* grad_coef, const float* found_inf, const float* skipped, const EmaHost* ema, void* stream) {
-    MC_CHECK(n_tensors >= 0 && (tensors || n_tensors == 0), "adamw: bad tensor list");
-    MC_CHECK(step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adamw: bad hyper-parameters");
-    // scalars are derived in double like torch does on the host (1 - 0.999 in fp32 is already 1.3e-5 off)
-    AdamScalars s;
-    s.lr_wd = (float)(lr * weight_decay);
-    s.beta1 = (float)beta1; s.beta2 = (float)beta2;
-    s.one_m_beta1 = (float)(1.0 - beta1); s.one_m_beta2 = (float)(1.0 - beta2);
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    s.step_size = (float)(lr / bc1);
-    s.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    s.eps = (float)eps;
-    AdamLs ls;
-    ls.found_inf = found_inf; ls.skipped = skipped; ls.lr = lr; ls.beta1 = beta1; ls.beta2 = beta2; ls.step = step;
-    ls.grad_coef = grad_coef;
-    AdamPack pk;
-    AdamEma em;
-    if (ema) { em.count = ema->count; em.decay = ema->decay; em.warmup = ema->warmup; }
-    int cnt = 0, chunks = 0;
-    auto flush = [&]() -> int {
-        if (cnt == 0) return MC_OK;
-        pk.first_chunk[cnt] = chunks;
-        if (ema)
-            hipLaunchKernelGGL((grad_coef ? adamw_multi_k<true, true> : adamw_multi_k<false, true>), dim3(chunks), dim3(256), 0,
-                               (hipStream_t)stream, pk, cnt, s, ls, em);
-        else
-            hipLaunchKernelGGL((grad_coef ? adamw_multi_k<true, false> : adamw_multi_k<false, false>), dim3(chunks), dim3(256), 0,
-                               (hipStream_t)stream, pk, cnt, s, ls, NoEma{});
-        MC_LAUNCH_CHECK();
-        cnt = 0; chunks = 0;
-        return MC_OK;
-    };
-    for (int i = 0; i < n_tensors; ++i) {
-        const mc_adamw_tensor& t = tensors[i];
-        if (t.numel == 0) continue;
-        MC_CHECK(t.param && t.grad && t.exp_avg && t.exp_avg_sq && t.numel > 0, "adamw: null tensor pointer");
-        const long long nch = (t.numel + CHUNK - 1) / CHUNK;
-        MC_CHECK(nch < (1ll << 30), "adamw: tensor too large");
-        if (cnt == PACK || (long long)chunks + nch > (1ll << 30)) {
-            int r = flush();
-            if (r != MC_OK) return r;
-        }
-        pk.p[cnt] = t.param; pk.g[cnt] = t.grad; pk.m[cnt] = t.exp_avg; pk.v[cnt] = t.exp_avg_sq;
-        pk.img[cnt] = t.bf16_image;
-        if (ema) em.e[cnt] = ema->shadows[i];
-        pk.n[cnt] = t.numel; pk.first_chunk[cnt] = chunks;
-        chunks += (int)nch;
-        ++cnt;
-    }
-    return flush();
-}
-}  // namespace

@@ -2,22 +2,18 @@
 // torch.optim.SGD over ALL parameters; trainer_ddp.py:300-303 steps it once per iteration].
 // HBM-bound: 12 B read + 8 B written per element with momentum (param, grad, buffer), 8 + 4 without; +2 B for a bf16 image the
 // pass rewrites from the updated parameter, +8 B for an EMA shadow that follows while the parameter is still in registers.
-// Packing as in optim.hip: up to PACK tensors per launch with their pointers as kernel arguments, a workgroup owns one CHUNK
-// of one tensor, found by a uniform scan over the pack's chunk prefix.  The tensor table is mc_adamw_tensor: exp_avg carries
-// the momentum buffer, exp_avg_sq is not read.
+// The packing of the tensor list into launches (a workgroup owns one CHUNK of one tensor) and the product, EMA and image
+// pieces are multi_tensor.h's.  The tensor table is mc_adamw_tensor: exp_avg carries the momentum buffer, exp_avg_sq is not read.
 //
 // Every operation of the rule (include/mammoclip_hip.h) is rounded to fp32 on its own, which is what the separate tensor
 // operations of torch give on any IEEE host.  The library is built with -ffp-contract=fast, so every product is written as
-// the instruction (the idiom of mul_rn / ema1 in optim.hip): a product the compiler cannot see cannot be fused into the sum
-// that consumes it.  tests/test_sgd_gpu.py compares the bits on every body.
+// the instruction (mul_rn of multi_tensor.h): a product the compiler cannot see cannot be fused into the sum that consumes it.
+// tests/test_sgd_gpu.py compares the bits on every body.
 #pragma clang fp contract(off)
-#include "common_hip.h"
+#include "multi_tensor.h"
 #include "../../include/mammoclip_hip.h"
 
 namespace {
-
-constexpr int PACK = 40;             // tensors per launch, as in optim.hip
-constexpr int CHUNK = 16384;         // elements per workgroup, as in optim.hip
 
 struct SgdPack {
     bf16_t* img[PACK];               // optional bf16 image of the updated parameter (nullptr: none)
@@ -25,8 +21,7 @@ struct SgdPack {
     const float* g[PACK];
     float* b[PACK];                  // momentum buffer (MOM only)
     float* e[PACK];                  // EMA shadow (EMA only)
-    int first_chunk[PACK + 1];       // prefix of chunk counts
-    long long n[PACK];
+    PackIndex ix;
 };
 
 struct SgdScalars {
@@ -42,23 +37,6 @@ struct SgdScalars {
     double ema_decay;
     int ema_warmup;
 };
-
-// a * b rounded once to fp32, as the instruction
-__device__ __forceinline__ float mul_rn(float a, float b) {
-    asm("v_mul_f32 %0, %1, %0" : "+v"(a) : "v"(b));
-    return a;
-}
-
-// w of the EMA update, exactly as ema_weight in optim.hip: (float)(1 - d_k) in double, k = *count + 1
-__device__ __forceinline__ float ema_weight(const long long* __restrict__ count, double decay, int warmup) {
-    double d = decay;
-    if (warmup) {
-        const double k = (double)(*count + 1);
-        const double r = (1.0 + k) / (10.0 + k);
-        if (r < d) d = r;
-    }
-    return (float)(1.0 - d);
-}
 
 struct SgdUniform {                  // what a workgroup derives once
     float c, w;
@@ -83,12 +61,6 @@ __device__ __forceinline__ void sgd4(float4& p, const float4& g, float4& b, cons
     sgd1<MOM>(p.x, g.x, b.x, s, u); sgd1<MOM>(p.y, g.y, b.y, s, u); sgd1<MOM>(p.z, g.z, b.z, s, u); sgd1<MOM>(p.w, g.w, b.w, s, u);
 }
 
-// e <- e + w * (p - e): sub, mul, add, each rounded (the contract of mc_ema_update)
-__device__ __forceinline__ void ema1(float& e, float p, float w) { e = e + mul_rn(p - e, w); }
-__device__ __forceinline__ void ema4(float4& e, const float4& p, float w) {
-    ema1(e.x, p.x, w); ema1(e.y, p.y, w); ema1(e.z, p.z, w); ema1(e.w, p.w, w);
-}
-
 // MOM: the momentum buffer is read (not on a first step) and written; EMA: the shadow follows.  Everything else is a uniform
 // branch on a kernel argument.  Body layout as adamw_multi_k: two float4 per array in flight, one float4, the ragged tail,
 // and the scalar body for pointers that are not 16-byte aligned (8 bytes for the image).
@@ -105,18 +77,20 @@ __global__ void __launch_bounds__(256) sgd_multi_k(SgdPack pk, int count, SgdSca
     u.c = u.clip ? *s.grad_coef : 1.f;
     u.w = 0.f;
     if constexpr (EMA) u.w = ema_weight(s.ema_count, s.ema_decay, s.ema_warmup);
+    // chunk_of_block of multi_tensor.h, written out: through the function the <MOM, EMA> = <true, true> instance waits for its
+    // loads at another place in the two-deep loop (profiles/optim_family_ab.md)
     int t = 0;
     const int blk = blockIdx.x;
-    while (t + 1 < count && pk.first_chunk[t + 1] <= blk) ++t;       // uniform scan, <= PACK scalar compares
-    const long long base = (long long)(blk - pk.first_chunk[t]) * CHUNK;
+    while (t + 1 < count && pk.ix.first_chunk[t + 1] <= blk) ++t;
+    const long long base = (long long)(blk - pk.ix.first_chunk[t]) * CHUNK;
     float* __restrict__ p = pk.p[t] + base;
     const float* __restrict__ g = pk.g[t] + base;
     float* __restrict__ b = MOM ? pk.b[t] + base : nullptr;
     float* __restrict__ e = EMA ? pk.e[t] + base : nullptr;
     bf16_t* __restrict__ img = pk.img[t] ? pk.img[t] + base : nullptr;      // base is a multiple of 16384: alignment kept
-    const long long left = pk.n[t] - base;
+    const long long left = pk.ix.n[t] - base;
     const int len = left < CHUNK ? (int)left : CHUNK;
-    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)b) | ((uintptr_t)e)) & 15) == 0 && (((uintptr_t)img) & 7) == 0;
+    const bool vec = (addr_bits(p, g, b, e) & 15) == 0 && (addr_bits(img) & 7) == 0;
     const bool load_b = MOM && !u.first;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     int i = threadIdx.x * 4;
@@ -134,10 +108,7 @@ __global__ void __launch_bounds__(256) sgd_multi_k(SgdPack pk, int count, SgdSca
                 ema4(E0, P0, u.w); ema4(E1, P1, u.w);
                 *(float4*)(e + i) = E0; *(float4*)(e + i + 1024) = E1;
             }
-            if (img) {
-                *(uint2*)(img + i) = make_uint2(pack_bf2(P0.x, P0.y), pack_bf2(P0.z, P0.w));
-                *(uint2*)(img + i + 1024) = make_uint2(pack_bf2(P1.x, P1.y), pack_bf2(P1.z, P1.w));
-            }
+            if (img) { store_image4(img + i, P0); store_image4(img + i + 1024, P1); }
         }
         for (; i + 3 < len; i += 1024) {
             float4 P0 = *(const float4*)(p + i);
@@ -149,7 +120,7 @@ __global__ void __launch_bounds__(256) sgd_multi_k(SgdPack pk, int count, SgdSca
             *(float4*)(p + i) = P0;
             if constexpr (MOM) *(float4*)(b + i) = B0;
             if constexpr (EMA) { ema4(E0, P0, u.w); *(float4*)(e + i) = E0; }
-            if (img) *(uint2*)(img + i) = make_uint2(pack_bf2(P0.x, P0.y), pack_bf2(P0.z, P0.w));
+            if (img) store_image4(img + i, P0);
         }
     }
     // vector path: the (< 4) elements after the last whole float4, one per lane; otherwise the whole chunk, lane-strided
@@ -159,7 +130,7 @@ __global__ void __launch_bounds__(256) sgd_multi_k(SgdPack pk, int count, SgdSca
         p[j] = P;
         if constexpr (MOM) b[j] = B;
         if constexpr (EMA) { float E = e[j]; ema1(E, P, u.w); e[j] = E; }
-        if (img) img[j] = f2bf(P);
+        if (img) store_image1(img + j, P);
     }
 }
 
@@ -188,7 +159,6 @@ extern "C" int mc_sgd_step(const mc_adamw_tensor* tensors, float* const* shadows
         if (t.numel == 0) continue;
         MC_CHECK(t.param && t.grad && (t.exp_avg || !mom), "sgd_step: null tensor pointer");
         MC_CHECK(!shadows || shadows[i], "sgd_step: null shadow pointer");
-        MC_CHECK((t.numel + CHUNK - 1) / CHUNK < (1ll << 30), "sgd_step: tensor too large");
     }
     SgdScalars s;
     s.lr = (float)lr; s.mu = (float)momentum; s.one_m_damp = (float)(1.0 - dampening); s.wd = (float)weight_decay;
@@ -198,32 +168,17 @@ extern "C" int mc_sgd_step(const mc_adamw_tensor* tensors, float* const* shadows
     s.step = step;
     s.grad_coef = grad_coef; s.found_inf = found_inf; s.skipped = skipped;
     s.ema_count = shadows ? count : nullptr; s.ema_decay = decay; s.ema_warmup = warmup != 0;
-    SgdPack pk;
-    int cnt = 0, chunks = 0;
-    auto flush = [&]() -> int {
-        if (cnt == 0) return MC_OK;
-        pk.first_chunk[cnt] = chunks;
-        auto k = mom ? (shadows ? sgd_multi_k<true, true> : sgd_multi_k<true, false>)
-                     : (shadows ? sgd_multi_k<false, true> : sgd_multi_k<false, false>);
-        hipLaunchKernelGGL(k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, s);
-        MC_LAUNCH_CHECK();
-        cnt = 0; chunks = 0;
-        return MC_OK;
-    };
-    for (int i = 0; i < n_tensors; ++i) {
-        const mc_adamw_tensor& t = tensors[i];
-        if (t.numel == 0) continue;
-        const long long nch = (t.numel + CHUNK - 1) / CHUNK;
-        if (cnt == PACK || (long long)chunks + nch > (1ll << 30)) {
-            int r = flush();
-            if (r != MC_OK) return r;
-        }
-        pk.p[cnt] = t.param; pk.g[cnt] = t.grad; pk.b[cnt] = mom ? t.exp_avg : nullptr;
-        pk.e[cnt] = shadows ? shadows[i] : nullptr;
-        pk.img[cnt] = t.bf16_image;
-        pk.n[cnt] = t.numel; pk.first_chunk[cnt] = chunks;
-        chunks += (int)nch;
-        ++cnt;
-    }
-    return flush();
+    auto k = mom ? (shadows ? sgd_multi_k<true, true> : sgd_multi_k<true, false>)
+                 : (shadows ? sgd_multi_k<false, true> : sgd_multi_k<false, false>);
+    return multi_tensor_launch<SgdPack>(
+        n_tensors, "sgd_step: tensor too large", [&](int i) { return tensors[i].numel; },
+        [&](SgdPack& pk, int slot, int i) {
+            const mc_adamw_tensor& t = tensors[i];
+            pk.p[slot] = t.param; pk.g[slot] = t.grad; pk.b[slot] = mom ? t.exp_avg : nullptr;
+            pk.e[slot] = shadows ? shadows[i] : nullptr;
+            pk.img[slot] = t.bf16_image;
+        },
+        [&](const SgdPack& pk, int cnt, int chunks, long long) {
+            hipLaunchKernelGGL(k, dim3(chunks), dim3(256), 0, (hipStream_t)stream, pk, cnt, s);
+        });
 }

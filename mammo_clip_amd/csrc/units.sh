@@ -5,6 +5,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused
 unit_headers() {      # $1 = unit: the headers its object depends on
   case $1 in
     gemm|gemm256|gemm256_tn) echo "$CSRC/common_hip.h $CSRC/../../include/mammoclip_hip.h $CSRC/gemm_tile.h" ;;
+    optim|optim_sgd) echo "$CSRC/common_hip.h $CSRC/../../include/mammoclip_hip.h $CSRC/multi_tensor.h" ;;
     *) echo "$CSRC/common_hip.h $CSRC/../../include/mammoclip_hip.h" ;;
   esac
 }

@@ -164,3 +164,32 @@ def test_entry_points_check_their_arguments():
         assert fails(lib.mc_adamw_step_ema(t, one, 1, *hyper, bad, 1, cp, None, None, None, None), b"adamw_step_ema: decay"), bad
     assert fails(lib.mc_ema_tick(None, None, None), b"ema_tick: null update count")
     assert cnt.value == 0
+
+
+@pytest.mark.parametrize("fault", ["null", "oversized"])
+def test_a_bad_tensor_past_the_first_pack_is_refused_before_any_launch(fault):
+    """41 tensors, the first 40 (one full launch) well formed at dummy addresses, the 41st with a null pointer or with 2^30
+    chunks: every entry point that walks the list returns MC_ERR_ARG with its own argument message, never a launch error.
+    The whole list is checked before the first launch; the addresses are not memory."""
+    lib = L.load()
+    P, CHUNK = 0x10000, 16384
+    t = (L.AdamwTensor * 41)()
+    for a in t:
+        a.param = a.grad = a.exp_avg = a.exp_avg_sq = P
+        a.numel = 8
+    shadows = (ctypes.c_void_p * 41)(*([P] * 41))
+    if fault == "null":
+        t[40].param = t[40].grad = t[40].exp_avg = t[40].exp_avg_sq = None
+    else:
+        t[40].numel = (1 << 30) * CHUNK
+    hyper = (1e-3, 0.9, 0.999, 1e-8, 0.0, 1)
+    big = 1 << 40                                  # doubles of a norm workspace that is never written
+    calls = [("adamw: null tensor pointer", lambda: lib.mc_adamw_step(t, 41, *hyper, None)),
+             ("adamw: null tensor pointer", lambda: lib.mc_adamw_step_ema(t, shadows, 41, *hyper, 0.9, 1, P, None, None, None, None)),
+             ("grads_unscale: null gradient pointer", lambda: lib.mc_grads_unscale(t, 41, 0.5, P, None)),
+             ("grad_norm: bad tensor list", lambda: lib.mc_grad_norm(t, 41, P, big, 1.0, P, None)),
+             ("grads_scale_dev: bad tensor list", lambda: lib.mc_grads_scale_dev(t, 41, P, None))]
+    for null_msg, call in calls:
+        want = null_msg if fault == "null" else ("adamw" if null_msg.startswith("adamw") else "grads_unscale") + ": tensor too large"
+        assert call() == 1, want                    # MC_ERR_ARG; a launch that failed would return MC_ERR_LAUNCH = 2
+        assert lib.mc_last_error().decode() == want
